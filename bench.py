@@ -4,7 +4,7 @@
 (BASELINE.json configs[2]; configs[3] when launched under torchrun with N ranks).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 32] [--size 512] [--dtype bf16]
-                    [--mode train|infer] [--no-cpu-baseline]
+                    [--mode train|infer] [--no-cpu-baseline] [--dump-outputs DIR]
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
   roofline     : the dominant kernel family (most GPU time in the profiled steps), its algorithmic
@@ -55,7 +55,11 @@ def main():
     ap.add_argument("--no-cpu-variants", action="store_true", help="skip the 4-thread / bs 8 CPU baseline variant")
     ap.add_argument("--prof-steps", type=int, default=3)
     ap.add_argument("--api-steps", type=int, default=10, help="timed steps of the drop-in API path (0 = skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # --gpus N without a launcher: start the N ranks ourselves (a child process, never an exec: nothing has touched the GPU yet, and
     # the child's ranks initialise it themselves), relay their output and exit with the launcher's code
@@ -146,6 +150,15 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
     last = [float(v) for v in out.flatten()[:3].tolist()] if args.mode == "train" else None
+    if args.dump_outputs and rank == 0:
+        # copied to the host now: the drop-in API and profile steps below move the weights again
+        if args.mode == "train":
+            arrays = {"loss": out, "logits": model.last_logits, "params": model.flat_params,
+                      "grads": model.flat_grads, "bn_buffers": model._flat["bufs"]}
+        else:
+            arrays = {"logits": out}
+        written = dump_outputs(args.dump_outputs, arrays)
+        _log(f"outputs of the last timed step written to {args.dump_outputs}: {written}")
 
     # ---- the same step through the drop-in API, and with the reference's per-step host sync
     api_ms = sync_ms = None
@@ -473,6 +486,32 @@ def latest_traffic(src_hash):
     if not loaded:
         raise FileNotFoundError("no profiles/rNN/traffic.json")
     return loaded[0]
+
+
+DUMP_BUDGET_BYTES = 60 << 20      # --dump-outputs: the .npy payloads, headers aside, stay under 64 MB
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES) -> dict:
+    """Write each tensor of `arrays` as out_dir/<name>.npy in float32, at most `budget` bytes in all.  Smallest first, an array
+    gets an equal share of what is left; one larger than its share is replaced by a fixed sample of its flattened elements
+    (positions drawn from a generator seeded with 0 and sorted), so the same shapes always sample the same positions.
+    Returns {name: (shape written, number of elements of the full array)}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    flat = {k: v.detach().float().reshape(-1) for k, v in arrays.items()}
+    left, written = budget // 4, {}
+    for i, (name, v) in enumerate(sorted(flat.items(), key=lambda kv: (kv[1].numel(), kv[0]))):
+        share = left // (len(flat) - i)
+        n = v.numel()
+        if n <= share:
+            a = arrays[name].detach().float().cpu().numpy()
+        else:
+            idx = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:share].sort().values
+            a = v[idx.to(v.device)].cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+        left -= a.size
+        written[name] = (list(a.shape), n)
+    return written
 
 
 def _log(msg):

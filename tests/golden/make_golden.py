@@ -20,7 +20,8 @@ Fixtures written next to this file:
 * ``loops_ref.json``     — returns of the REFERENCE's own ``train_one_epoch`` (train.py:381-459) and ``validate``
                            (train.py:461-529) run here on CPU over three seeded (2, 2, 1)-image batches at 64 x 64 with the oracle
                            network, torch AdamW / BCE and the oracle's DiceLoss; per-step loss components, parameter checksums
-                           and encoder.bn1 running statistics (G4/G5).  Pins the oracle's loop restatements.
+                           and encoder.bn1 running statistics (G4/G5), in fp32 and (key "float64") in float64.  Pins the
+                           oracle's loop restatements (float64: the same on every CPU) and the engine's fp32 epoch.
 
 * ``real_masks.npz``     — eight of the reference's own hand-labelled masks (data/masks/*.png: data files, mode L),
                            binarised `> 0` as train.py:163-170 reads them and bit-packed: real indentation shapes
@@ -98,13 +99,13 @@ class _Recorder(torch.nn.Module):
 LOOPS_THREADS = 4      # the reference's own setting (train.py:19); the CPU test pins the same count
 
 
-def loops_batches():
+def loops_batches(dtype=torch.float32):
     """The loaders of the loop fixture: what a DataLoader over the reference's dataset yields, (x, y, names) — three training
     batches of 2, 2 and 1 images (a ragged last batch exercises the sample-weighted epoch mean, train.py:452-459) and two
     validation batches — at 64 x 64, seeded."""
-    x, y = O.synthetic_batch(5, 64, seed=1234)
+    x, y = (t.to(dtype) for t in O.synthetic_batch(5, 64, seed=1234))
     train = [(x[0:2], y[0:2], ["a", "b"]), (x[2:4], y[2:4], ["c", "d"]), (x[4:5], y[4:5], ["e"])]
-    xv, yv = O.synthetic_batch(3, 64, seed=4321)
+    xv, yv = (t.to(dtype) for t in O.synthetic_batch(3, 64, seed=4321))
     val = [(xv[0:2], yv[0:2], ["v0", "v1"]), (xv[2:3], yv[2:3], ["v2"])]
     return train, val
 
@@ -112,21 +113,29 @@ def loops_batches():
 def loops_ref():
     """G4/G5: the REFERENCE's own `train_one_epoch` (train.py:381-459) and `validate` (train.py:461-529), executed here on CPU,
     driving the oracle network (the reference's network class lives in the absent smp package) with torch's AdamW / BCE and the
-    oracle's DiceLoss: returns, per-step loss components, parameter checksums and BatchNorm running statistics."""
+    oracle's DiceLoss: returns, per-step loss components, parameter checksums and BatchNorm running statistics.  Top level: the
+    reference's own fp32 run.  "float64": the same loops with the network and the batches in float64, whose results do not depend
+    on which CPU kernels torch picks on a given machine (fp32 ones differ in the last bits between CPU vendors)."""
     ref_train = _import_reference_train()
     torch.set_num_threads(LOOPS_THREADS)
+    out = {"threads": LOOPS_THREADS, "torch": torch.__version__, **_reference_loops(ref_train, torch.float32),
+           "float64": _reference_loops(ref_train, torch.float64)}
+    json.dump(out, open(HERE / "loops_ref.json", "w"), indent=1)
+    print("loops_ref:", out["train_one_epoch"], out["validate"], "float64:", out["float64"]["train_one_epoch"])
+
+
+def _reference_loops(ref_train, dtype):
     O.set_seed(42)
-    model = O.build_model()
+    model = O.build_model().to(dtype)
     opt = torch.optim.AdamW(model.parameters(), lr=5e-5, weight_decay=1e-4)          # train.py:606
     bce, dice = _Recorder(torch.nn.BCEWithLogitsLoss()), _Recorder(O.DiceLoss(mode="binary"))   # train.py:600-601
-    train, val = loops_batches()
+    train, val = loops_batches(dtype)
     epoch_loss = ref_train.train_one_epoch(model, train, opt, bce, dice, "cpu", scaler=None)
     steps = [{"bce": b, "dice": d} for b, d in zip(bce.values, dice.values)]
     bce.values, dice.values = [], []
     v_loss, v_dice, v_iou = ref_train.validate(model, val, bce, dice, "cpu", out_vis_dir=None)
     named = dict(model.named_parameters())
-    out = {
-        "threads": LOOPS_THREADS, "torch": torch.__version__,
+    return {
         "train_one_epoch": epoch_loss, "train_steps": steps,
         "validate": {"loss": v_loss, "dice": v_dice, "iou": v_iou,
                      "steps": [{"bce": b, "dice": d} for b, d in zip(bce.values, dice.values)]},
@@ -137,8 +146,6 @@ def loops_ref():
         "bn1_running_var": model.encoder.bn1.running_var.double().tolist(),
         "bn1_num_batches_tracked": int(model.encoder.bn1.num_batches_tracked),
     }
-    json.dump(out, open(HERE / "loops_ref.json", "w"), indent=1)
-    print("loops_ref:", epoch_loss, (v_loss, v_dice, v_iou))
 
 
 def manifest_and_small():

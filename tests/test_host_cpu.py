@@ -215,11 +215,38 @@ def test_bench_launch_plan_and_config_labels():
     assert bench.baseline_config_index("train", 512, "fp32", 32, 1) is None
 
 
+def test_bench_dump_outputs_budget_and_sampling(tmp_path):
+    """bench.py --dump-outputs: float32 .npy files within the byte budget (the default stays under 64 MB); an array that fits keeps
+    its shape, a larger one becomes the same seeded sample of its flattened elements on every call."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("vk_bench", ROOT / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert bench.DUMP_BUDGET_BYTES < 64 * 10 ** 6
+    g = torch.Generator().manual_seed(5)
+    arrays = {"loss": torch.rand(3, generator=g), "logits": torch.randn(2, 1, 32, 32, generator=g),
+              "params": torch.randn(10_000, generator=g)}
+    budget = 4 * 5000
+    written = bench.dump_outputs(tmp_path / "a", arrays, budget=budget)
+    bench.dump_outputs(tmp_path / "b", arrays, budget=budget)
+    assert written == {"loss": ([3], 3), "logits": ([2, 1, 32, 32], 2048), "params": ([2949], 10_000)}
+    assert sum((tmp_path / "a" / f"{k}.npy").stat().st_size - 128 for k in arrays) <= budget      # 128-byte .npy headers
+    for k, v in arrays.items():
+        a, b = np.load(tmp_path / "a" / f"{k}.npy"), np.load(tmp_path / "b" / f"{k}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, b)
+        if k != "params":
+            assert np.array_equal(a, v.numpy())
+    p = np.load(tmp_path / "a" / "params.npy")
+    assert np.isin(p, arrays["params"].numpy()).all() and len(np.unique(p)) == p.size
+
+
 def test_bench_self_launch_spawns_ranks_and_relays_exit_code(tmp_path, monkeypatch):
     """The spawn path end to end without a GPU: `bench.py --gpus 2` (no WORLD_SIZE) starts torch.distributed.run with two ranks;
     each rank gets as far as the "needs an MI355X" refusal here, and the parent exits with the launcher's non-zero code."""
     import subprocess, sys, os
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    env["HIP_VISIBLE_DEVICES"] = "-1"     # no device for the ranks on a machine that has one too: the suite runs in full there
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"], env=env,
                        capture_output=True, text=True, timeout=300)
     assert r.returncode != 0

@@ -9,11 +9,13 @@
  *   vk_unet_forward ........................... model(x)                     train.py:436, 510, 693; infer_pth_gui.py:51
  *   vk_unet_loss .............................. bce(logits,y)+dice(logits,y) train.py:438, 513 (600-601)
  *   vk_unet_backward .......................... loss.backward()              train.py:443, 448
+ *   vk_unet_set_trainable ..................... p.requires_grad_(False) before backward (fine-tuning with a frozen encoder)
  *   vk_seg_metrics ............................ dice_coef / iou_coef (validate) train.py:230-281, 518-522
  *   vk_comm_* / vk_allreduce_bucket ........... (no reference counterpart: the 8-GPU data-parallel exchange)
  *   vk_adamw_step ............................. optimizer.step()/zero_grad   train.py:428, 449 (606)
  *   vk_amp_check_inf / vk_amp_unscale_check /
  *   vk_adamw_step_amp ......................... GradScaler unscale + inf check + skipped step  train.py:441-445 (610-611)
+ *   vk_adamw_step_amp_segments ................ the same over the tensors that have a gradient (frozen ones are skipped)
  *   vk_conv_fwd / vk_conv_wgrad / ... ......... the ATen operators the reference dispatches to
  *                                               (conv2d, batch_norm, relu, max_pool2d, interpolate, cat)
  *   vk_conv_fwd_splitk ........................ the same convolutions at batch 1 (predict_mask / Segmenter.infer)
@@ -432,6 +434,20 @@ int vk_amp_unscale_check(size_t n, float* grad, const float* inv_scale, float* f
 int vk_adamw_step_amp(size_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
                       float beta2, float eps, float weight_decay, int* step_count, float inv_scale, const float* grad_scale,
                       const float* found_inf, float* scratch4, void* lowp_copy, vk_dtype lowp_dtype, void* stream);
+/* Per-tensor AdamW (fine-tuning: torch skips a parameter whose grad is None and keeps one state["step"] per parameter).
+ * segments (device): int64 [n_segments][3] = {elem_begin, elem_end, tensor_index} of the flat buffers, each tensor_index at most
+ * once; step_counts (device): int32 per tensor_index, advanced like vk_adamw_step_amp's *step_count (not on an overflow) and driving
+ * that segment's bias corrections.  blocks (device): int32 [n_blocks][2] = {segment, chunk}, one workgroup per chunk of
+ * VK_ADAMW_SEGMENT_CHUNK elements, as vk_adamw_segment_blocks builds it on the host.  scratch: float[4 + 2 n_segments] device
+ * scratch.  Element arithmetic, GradScaler protocol (grad_scale / found_inf / inv_scale) and skip rule are vk_adamw_step_amp's.
+ * vk_adamw_segment_blocks (host only): writes the block table of `segments_host` into blocks_host (capacity rows; NULL: count
+ * only) and returns the number of rows, or <0 on a bad segment. */
+#define VK_ADAMW_SEGMENT_CHUNK 4096
+int vk_adamw_segment_blocks(int n_segments, const int64_t* segments_host, int32_t* blocks_host, int capacity);
+int vk_adamw_step_amp_segments(int n_segments, const int64_t* segments, int n_blocks, const int32_t* blocks, float* param,
+                               const float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2, float eps,
+                               float weight_decay, int* step_counts, float inv_scale, const float* grad_scale,
+                               const float* found_inf, float* scratch, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Engine level: the whole network as one plan
@@ -488,8 +504,17 @@ int vk_unet_loss(vk_unet* h, const float* logits, const float* target, float* lo
                  float w_bce, float w_dice, void* stream);
 /* dlogits: fp32 [N][1][S][S] gradient of the loss wrt the logits, or NULL to use the one vk_unet_loss
  * left in the workspace.  Runs backward stages [stage_begin, stage_end); stage i completes gradient bucket i.  Gradients are
- * accumulated into the flat grad buffer (caller zeroes it once per step, e.g. via vk_unet_zero_grad). */
+ * accumulated into the flat grad buffer (caller zeroes it once per step, e.g. via vk_unet_zero_grad).
+ * Only the gradients of TRAINABLE tensors (vk_unet_set_trainable) are written; the element ranges of frozen tensors are left
+ * untouched, so after a zeroing they stay exactly zero.  A launch runs only if something it writes is needed: a weight or
+ * gamma / beta gradient iff its tensor is trainable, a data gradient or BatchNorm-backward pass iff a trainable tensor lies at or
+ * behind it in the backward order (head, decoder blocks 4..0, encoder blocks layer4.2 .. layer1.0, stem).  Stages behind the last
+ * trainable tensor are no-ops that return VK_OK. */
 int vk_unet_backward(vk_unet* h, const float* dlogits, int stage_begin, int stage_end, void* stream);
+/* Fine-tuning: one flag per parameter tensor (kinds 0 and 1 of vk_unet_tensor_info, in table order; nonzero = trainable, i.e.
+ * torch's requires_grad).  n must be the number of parameter tensors (140), else VK_ERR_ARG.  Host-only; takes effect at the next
+ * vk_unet_backward.  A new plan starts with every tensor trainable, which is the unpruned schedule. */
+int vk_unet_set_trainable(vk_unet* h, const uint8_t* flags, int n);
 int vk_unet_zero_grad(vk_unet* h, void* stream);
 
 /* ------------------------------------------------------------------------------------------------

@@ -132,6 +132,8 @@ SIGNATURES = {
     "vk_amp_check_inf": (ci, [sz, vp, vp, vp]),
     "vk_amp_unscale_check": (ci, [sz, vp, vp, vp, vp]),
     "vk_adamw_step_amp": (ci, [sz, vp, vp, vp, vp, cf, cf, cf, cf, cf, vp, cf, vp, vp, vp, vp, ci, vp]),
+    "vk_adamw_segment_blocks": (ci, [ci, P(i64), P(C.c_int32), ci]),
+    "vk_adamw_step_amp_segments": (ci, [ci, vp, ci, vp, vp, vp, vp, vp, cf, cf, cf, cf, cf, vp, cf, vp, vp, vp, vp]),
     "vk_unet_create": (ci, [P(vk_unet_config), P(vp)]),
     "vk_unet_destroy": (None, [vp]),
     "vk_unet_set_side_stream": (ci, [vp, ci]),
@@ -147,6 +149,7 @@ SIGNATURES = {
     "vk_unet_forward": (ci, [vp, vp, vp, ci, vp]),
     "vk_unet_loss": (ci, [vp, vp, vp, vp, cf, cf, cf, vp]),
     "vk_unet_backward": (ci, [vp, vp, ci, ci, vp]),
+    "vk_unet_set_trainable": (ci, [vp, P(C.c_uint8), ci]),
     "vk_unet_zero_grad": (ci, [vp, vp]),
     "vk_unet_debug_tensor": (ci, [vp, C.c_char_p, P(vp), P(ci * 4)]),
     "vk_comm_unique_id": (ci, [vp]),

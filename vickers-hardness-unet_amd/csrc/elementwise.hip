@@ -1221,6 +1221,28 @@ __global__ void k_adamw_prepare(int* __restrict__ step_count, const float* __res
   st[3] = grad_scale ? (float)((double)inv_scale / (double)*grad_scale) : inv_scale;
 }
 
+// one element of k_adamw_segments: k_adamw_dev's expression with its fused multiply-adds spelled out and contraction off.  They are
+// exactly the ones the compiler forms in k_adamw_dev's loop (g*inv - m, m + d*(1 - beta1), gi*((1 - beta2)*gi) + v*beta2,
+// p*(1 - lr*wd) - step*ratio); written as plain source the vectoriser pairs this loop's products into v_pk_mul_f32 instead and
+// rounds them separately.  So the two kernels agree bit for bit (tests/test_frozen_params_gpu.py holds them to it).
+__device__ __forceinline__ float adamw_elem(size_t i, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                            float* __restrict__ v, float lr, float beta1, float beta2, float eps, float wd, float step_size,
+                                            float bc2_sqrt, float inv_scale) {
+#pragma clang fp contract(off)
+  const float gr = g[i];
+  const float gi = gr * inv_scale;
+  const float keep = __builtin_fmaf(-lr, wd, 1.f);                                  // 1 - lr*wd
+  float mi = m[i];
+  mi = __builtin_fmaf(__builtin_fmaf(gr, inv_scale, -mi), 1.f - beta1, mi);        // m + (gi - m)*(1 - beta1)
+  const float vi = __builtin_fmaf(gi, (1.f - beta2) * gi, v[i] * beta2);          // v*beta2 + (1 - beta2)*gi*gi
+  const float denom = sqrtf(vi) / bc2_sqrt + eps;
+  const float pi = __builtin_fmaf(p[i], keep, -(step_size * (mi / denom)));        // p*(1 - lr*wd) - step*(m / denom)
+  p[i] = pi;
+  m[i] = mi;
+  v[i] = vi;
+  return pi;
+}
+
 template <typename LT>
 __global__ void k_adamw_dev(size_t n, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                             float lr, float beta1, float beta2, float eps, float wd, const float* __restrict__ st, LT* lowp) {
@@ -1239,6 +1261,44 @@ __global__ void k_adamw_dev(size_t n, float* __restrict__ p, const float* __rest
     v[i] = vi;
     if (lowp) st1(lowp + i, pi);
   }
+}
+
+// Per-tensor AdamW (vk_adamw_step_amp_segments).  Prepare: k_adamw_prepare once per segment — its tensor's counter advances unless
+// the step is skipped, and st[4 + 2s], st[5 + 2s] = lr / (1 - beta1^t), sqrt(1 - beta2^t) of that counter; st[0], st[3] as there.
+__global__ __launch_bounds__(256) void k_adamw_prepare_segments(int nseg, const int64_t* __restrict__ seg, int* __restrict__ steps,
+                                                                const float* __restrict__ grad_scale, const float* __restrict__ found_inf,
+                                                                float lr, float beta1, float beta2, float inv_scale, float* __restrict__ st) {
+  const bool skip = found_inf && *found_inf != 0.f;
+  if (threadIdx.x == 0) {
+    st[0] = skip ? 1.f : 0.f;
+    st[1] = st[2] = 0.f;
+    st[3] = grad_scale ? (float)((double)inv_scale / (double)*grad_scale) : inv_scale;
+  }
+  for (int s = threadIdx.x; s < nseg; s += blockDim.x) {
+    int* const cnt = steps + seg[3 * (size_t)s + 2];
+    int t = *cnt;
+    if (!skip) {
+      t += 1;
+      *cnt = t;
+    }
+    const double bc1 = 1.0 - pow((double)beta1, (double)(t > 0 ? t : 1));
+    const double bc2 = 1.0 - pow((double)beta2, (double)(t > 0 ? t : 1));
+    st[4 + 2 * s] = (float)((double)lr / bc1);
+    st[5 + 2 * s] = (float)sqrt(bc2);
+  }
+}
+
+// Update: workgroup b owns chunk blocks[b].y of segment blocks[b].x (a table built once per set of segments: no search per element)
+__global__ __launch_bounds__(256) void k_adamw_segments(const int64_t* __restrict__ seg, const int2* __restrict__ blocks, float* __restrict__ p,
+                                                        const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, float lr,
+                                                        float beta1, float beta2, float eps, float wd, const float* __restrict__ st) {
+  if (st[0] != 0.f) return;
+  const int2 b = blocks[blockIdx.x];
+  const int64_t begin = seg[3 * (size_t)b.x] + (int64_t)b.y * VK_ADAMW_SEGMENT_CHUNK;
+  const int64_t end = min(begin + (int64_t)VK_ADAMW_SEGMENT_CHUNK, seg[3 * (size_t)b.x + 1]);
+  const float step_size = st[4 + 2 * b.x], bc2_sqrt = st[5 + 2 * b.x], inv_scale = st[3];
+  for (int64_t i = begin + threadIdx.x; i < end; i += blockDim.x)
+    (void)adamw_elem((size_t)i, p, g, m, v, lr, beta1, beta2, eps, wd, step_size, bc2_sqrt, inv_scale);
 }
 
 }  // namespace vk
@@ -1570,6 +1630,41 @@ extern "C" int vk_adamw_step_amp(size_t n, float* param, const float* grad, floa
     hipLaunchKernelGGL(k_adamw_dev<f16_t>, grid, block, 0, st, n, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay,
                        (const float*)scratch4, (f16_t*)lowp_copy);
   }
+  VK_CHECK_HIP(hipGetLastError());
+  return VK_OK;
+}
+
+extern "C" int vk_adamw_segment_blocks(int n_segments, const int64_t* seg, int32_t* blocks, int capacity) {
+  VK_CHECK_ARG(n_segments >= 1 && seg && (capacity >= 0), "vk_adamw_segment_blocks: bad argument");
+  int64_t rows = 0;
+  for (int s = 0; s < n_segments; ++s) {
+    const int64_t b = seg[3 * s], e = seg[3 * s + 1];
+    VK_CHECK_ARG(0 <= b && b < e && seg[3 * s + 2] >= 0, "vk_adamw_segment_blocks: bad segment %d [%lld, %lld)", s, (long long)b, (long long)e);
+    const int64_t chunks = (e - b + VK_ADAMW_SEGMENT_CHUNK - 1) / VK_ADAMW_SEGMENT_CHUNK;
+    for (int64_t c = 0; c < chunks; ++c, ++rows) {
+      VK_CHECK_ARG(rows < (1 << 30), "vk_adamw_segment_blocks: too many blocks");
+      if (blocks && rows < capacity) {
+        blocks[2 * rows] = s;
+        blocks[2 * rows + 1] = (int32_t)c;
+      }
+    }
+  }
+  VK_CHECK_ARG(!blocks || rows <= capacity, "vk_adamw_segment_blocks: %lld rows do not fit in %d", (long long)rows, capacity);
+  return (int)rows;
+}
+
+extern "C" int vk_adamw_step_amp_segments(int n_segments, const int64_t* segments, int n_blocks, const int32_t* blocks, float* param,
+                                          const float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2, float eps,
+                                          float weight_decay, int* step_counts, float inv_scale, const float* grad_scale,
+                                          const float* found_inf, float* scratch, void* stream) {
+  VK_CHECK_ARG(n_segments >= 1 && n_blocks >= 1 && segments && blocks && param && grad && exp_avg && exp_avg_sq && step_counts && scratch,
+               "vk_adamw_step_amp_segments: bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_adamw_prepare_segments, dim3(1), dim3(256), 0, st, n_segments, segments, step_counts, grad_scale, found_inf, lr, beta1,
+                     beta2, inv_scale, scratch);
+  vkh::ProfScope ps_("adamw_segments", st, 0.0, (double)n_blocks * VK_ADAMW_SEGMENT_CHUNK * 28.0);
+  hipLaunchKernelGGL(k_adamw_segments, dim3((unsigned)n_blocks), dim3(256), 0, st, segments, (const int2*)blocks, param, grad, exp_avg, exp_avg_sq,
+                     lr, beta1, beta2, eps, weight_decay, (const float*)scratch);
   VK_CHECK_HIP(hipGetLastError());
   return VK_OK;
 }

@@ -318,6 +318,8 @@ struct ConvL {
   int bn;                 // following BN (-1 for the head)
   int Hin, Hout;          // spatial sizes: rows ...
   int Win, Wout;          // ... and columns (r04: H != W allowed, both divisible by 32)
+  int w_t = -1, b_t = -1; // parameter-tensor index (vk_unet_set_trainable order) of the weight / the bias (head only)
+  int rank = 0;           // position of the weight in the backward order (assign_backward_ranks)
   // workspace
   char* z = nullptr;      // raw conv output [N][Hout][Hout][K]
   char* g = nullptr;      // gradient wrt activated output, overwritten in place by gradient wrt z
@@ -328,6 +330,8 @@ struct BnL {
   int C;
   int64_t g_off, b_off, rm_off, rv_off;
   int idx;
+  int g_t = -1, b_t = -1; // parameter-tensor indices of gamma / beta
+  int rank = 0;           // position in the backward order (gamma and beta share it)
   double count;           // N*H*W
   // workspace
   double* stats = nullptr;      // [2C] forward sums
@@ -368,11 +372,19 @@ using namespace vk;
 constexpr int kMaxStages = 16;
 constexpr int kMaxBatch = 40;                       // layers in one batched weight-gradient launch (the model has 35 of the class)
 constexpr size_t kEngineSlabBytes = 176u << 20;     // slab workspace of a training plan: partial tiles of a whole-backward batch (~950 x 147 KB)
+constexpr size_t kGradScratchFloats = 2048;         // frozen-gradient sink: dgamma [512] | dbeta [512] | head dw [144] | head db
 
 struct vk_unet {
   vk_unet_config cfg;
   int eb;                        // element bytes of the activation dtype
   std::vector<vk_tensor_info> infos;
+  int n_ptensors = 0;            // parameter tensors (kinds 0 and 1) in `infos`
+  // fine-tuning (vk_unet_set_trainable): one flag per parameter tensor; a backward launch runs only if something it writes is needed —
+  // a weight / gamma / beta gradient iff its tensor is trainable, a data gradient or BN-backward pass iff some trainable tensor lies at
+  // or behind it in the backward order (ranks: assign_backward_ranks).  All trainable (the default) is the unpruned schedule.
+  std::vector<uint8_t> trainable;
+  int last_rank = 0;             // highest rank of a trainable tensor; -1: none
+  unsigned mask_version = 0;     // bumped by every change of `trainable` (keys the batched weight-gradient tables)
   std::vector<ConvL> convs;
   std::vector<BnL> bns;
   std::vector<BlockL> blocks;
@@ -415,6 +427,7 @@ struct vk_unet {
   struct WPlan {
     bool built = false;
     int target = 0, n = 0;
+    unsigned version = 0;           // mask_version the tables were built for (the same n can be another set of layers)
     vk::WgradBatchPlan plan;
   };
   std::vector<WItem> pending;
@@ -423,6 +436,7 @@ struct vk_unet {
   std::vector<PackEntry> pack_tab;
   std::vector<CastRange> cast_tab;
   size_t off_tab_cast = 0;
+  size_t off_gscratch = 0;          // sink of the gamma / beta / head gradients of frozen tensors (never read)
   std::vector<BnEvalEntry> bn_tab;
   std::map<std::string, std::pair<void*, std::vector<int>>> debug;
 
@@ -433,7 +447,17 @@ namespace {
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-void add_info(vk_unet* h, const std::string& name, int kind, std::vector<int> dims, int64_t offset, int64_t numel) {
+// fine-tuning (vk_unet_set_trainable): is anything at or behind `rank` in the backward order trainable / is tensor t trainable; the
+// gradient slot of a frozen gamma / beta / head tensor is the never-read sink, so its range of the flat buffer stays exactly zero
+bool need_from(const vk_unet* h, int rank) { return h->last_rank >= rank; }
+bool trains(const vk_unet* h, int t) { return h->trainable[(size_t)t] != 0; }
+float* grad_or_sink(vk_unet* h, int t, int64_t off, int sink_off) {
+  return trains(h, t) ? h->grads + off : (float*)(h->ws + h->off_gscratch) + sink_off;
+}
+float* dgamma_of(vk_unet* h, const BnL& b) { return grad_or_sink(h, b.g_t, b.g_off, 0); }
+float* dbeta_of(vk_unet* h, const BnL& b) { return grad_or_sink(h, b.b_t, b.b_off, 512); }
+
+int add_info(vk_unet* h, const std::string& name, int kind, std::vector<int> dims, int64_t offset, int64_t numel) {
   vk_tensor_info ti;
   memset(&ti, 0, sizeof(ti));
   snprintf(ti.name, sizeof(ti.name), "%s", name.c_str());
@@ -443,6 +467,7 @@ void add_info(vk_unet* h, const std::string& name, int kind, std::vector<int> di
   ti.offset = offset;
   ti.numel = numel;
   h->infos.push_back(ti);
+  return kind <= 1 ? h->n_ptensors++ : -1;
 }
 
 int add_conv(vk_unet* h, const std::string& name, int Cin, int K, int R, int stride, int pad, int Hin, int Win, bool bias = false) {
@@ -456,10 +481,10 @@ int add_conv(vk_unet* h, const std::string& name, int Cin, int K, int R, int str
   c.wd_off = -1;
   c.bn = -1;
   const int64_t numel = (int64_t)K * Cin * R * R;
-  add_info(h, name + ".weight", 0, {K, Cin, R, R}, c.w_off, numel);
+  c.w_t = add_info(h, name + ".weight", 0, {K, Cin, R, R}, c.w_off, numel);
   h->n_params += (int64_t)align_up((size_t)numel, 4);
   if (bias) {
-    add_info(h, name + ".bias", 1, {K}, h->n_params, K);
+    c.b_t = add_info(h, name + ".bias", 1, {K}, h->n_params, K);
     h->n_params += 4;
   }
   h->convs.push_back(c);
@@ -473,10 +498,10 @@ int add_bn(vk_unet* h, const std::string& name, int C, double count) {
   b.count = count;
   b.idx = (int)h->bns.size();
   b.g_off = h->n_params;
-  add_info(h, name + ".weight", 1, {C}, b.g_off, C);
+  b.g_t = add_info(h, name + ".weight", 1, {C}, b.g_off, C);
   h->n_params += C;
   b.b_off = h->n_params;
-  add_info(h, name + ".bias", 1, {C}, b.b_off, C);
+  b.b_t = add_info(h, name + ".bias", 1, {C}, b.b_off, C);
   h->n_params += C;
   b.rm_off = h->n_bufs;
   add_info(h, name + ".running_mean", 2, {C}, b.rm_off, C);
@@ -575,6 +600,31 @@ void build_topology(vk_unet* h) {
   h->buckets.push_back({0, block_start[3]});                     // 9: layer1 + stem
 }
 
+// Backward order of the parameter tensors (the order backward_stage visits them; the head's weight and bias share rank 0): a data
+// gradient is needed iff a trainable tensor has a higher rank than the weight of its convolution — the linear order is conservative
+// where the graph branches (a trainable downsample conv keeps its block's conv2 data gradient alive), never wrong
+void assign_backward_ranks(vk_unet* h) {
+  int r = 0;
+  auto conv = [&](int i) { h->convs[(size_t)i].rank = r++; };
+  auto bn = [&](int i) { h->bns[(size_t)h->convs[(size_t)i].bn].rank = r++; };
+  conv(h->head_conv);
+  for (int i = 4; i >= 0; --i) {
+    const DecL& d = h->decs[(size_t)i];
+    bn(d.conv2); conv(d.conv2); bn(d.conv1); conv(d.conv1);
+  }
+  for (int bi = 15; bi >= 0; --bi) {
+    const BlockL& k = h->blocks[(size_t)bi];
+    bn(k.conv2);
+    if (k.convd >= 0) bn(k.convd);
+    conv(k.conv2);
+    if (k.convd >= 0) conv(k.convd);
+    bn(k.conv1); conv(k.conv1);
+  }
+  bn(h->stem_conv); conv(h->stem_conv);
+  h->trainable.assign((size_t)h->n_ptensors, 1);
+  h->last_rank = r - 1;
+}
+
 void layout_workspace(vk_unet* h) {
   const int N = h->cfg.N, S = h->cfg.size, SW = h->cfg.width, eb = h->eb;
   const bool tr = h->cfg.training != 0;
@@ -639,6 +689,7 @@ void layout_workspace(vk_unet* h) {
   h->off_tab_pack = take(h->convs.size() * sizeof(PackEntry));
   h->off_tab_cast = take(h->convs.size() * sizeof(CastRange));
   h->off_tab_bn = take(h->bns.size() * sizeof(BnEvalEntry));
+  h->off_gscratch = tr ? take(kGradScratchFloats * sizeof(float)) : 0;      // last: every other offset is what it was without it
   h->ws_bytes = off;
 }
 
@@ -786,6 +837,7 @@ extern "C" int vk_unet_create(const vk_unet_config* cfg, vk_unet** out) {
   h->cfg.width = width;
   h->eb = cfg->dtype == VK_F32 ? 4 : 2;
   build_topology(h);
+  assign_backward_ranks(h);
   layout_workspace(h);
   *out = h;
   return VK_OK;
@@ -951,6 +1003,27 @@ extern "C" int vk_unet_set_side_stream(vk_unet* h, int enable) {
   return VK_OK;
 }
 
+extern "C" int vk_unet_set_trainable(vk_unet* h, const uint8_t* flags, int n) {
+  VK_CHECK_ARG(h && flags, "vk_unet_set_trainable: null argument");
+  VK_CHECK_ARG(n == h->n_ptensors, "vk_unet_set_trainable: %d flags for %d parameter tensors", n, h->n_ptensors);
+  bool changed = false;
+  for (int t = 0; t < n; ++t) {
+    const uint8_t v = flags[t] ? 1 : 0;
+    changed |= v != h->trainable[(size_t)t];
+    h->trainable[(size_t)t] = v;
+  }
+  if (!changed) return VK_OK;
+  h->last_rank = -1;
+  for (const ConvL& c : h->convs) {
+    if (trains(h, c.w_t) || (c.b_t >= 0 && trains(h, c.b_t))) h->last_rank = std::max(h->last_rank, c.rank);
+  }
+  for (const BnL& b : h->bns) {
+    if (trains(h, b.g_t) || trains(h, b.b_t)) h->last_rank = std::max(h->last_rank, b.rank);
+  }
+  ++h->mask_version;
+  return VK_OK;
+}
+
 extern "C" int vk_unet_zero_grad(vk_unet* h, void* stream) {
   VK_CHECK_ARG(h && h->bound && h->grads, "vk_unet_zero_grad: no gradient buffer bound");
   VK_CHECK_HIP(hipMemsetAsync(h->grads, 0, (size_t)h->n_params * sizeof(float), (hipStream_t)stream));
@@ -1071,8 +1144,8 @@ int bn_bwd_phase2(vk_unet* h, BnL& b, int C, size_t pixels, const void* dy, cons
   static const int maxc = getenv("VK_BN_APPLY_FUSED_MAXC") ? atoi(getenv("VK_BN_APPLY_FUSED_MAXC")) : VK_BN_APPLY_FUSED_MAXC_DEFAULT;
   if (C <= maxc)
     return vk_bn_bwd_apply_fused(h->cfg.dtype, pixels, C, dy, z, mask_mode, b.scale, b.shift, mask_src, b.bsums, b.count, h->params + b.g_off,
-                                 b.mean, b.invstd, h->grads + b.g_off, h->grads + b.b_off, dz, g_out, g_acc, st);
-  RET_IF(vk_bn_bwd_coeffs(C, b.bsums, b.count, h->params + b.g_off, b.mean, b.invstd, h->grads + b.g_off, h->grads + b.b_off, b.coef, st));
+                                 b.mean, b.invstd, dgamma_of(h, b), dbeta_of(h, b), dz, g_out, g_acc, st);
+  RET_IF(vk_bn_bwd_coeffs(C, b.bsums, b.count, h->params + b.g_off, b.mean, b.invstd, dgamma_of(h, b), dbeta_of(h, b), b.coef, st));
   return vk_bn_bwd_apply(h->cfg.dtype, pixels, C, dy, z, mask_mode, b.scale, b.shift, mask_src, b.coef, dz, g_out, g_acc, st);
 }
 
@@ -1190,21 +1263,28 @@ int backward_decoder(vk_unet* h, int i, hipStream_t st) {
     skip = bn_act(h, stem);
     g_skip = stem.g;
   }
+  const BnL& bn1 = h->bns[c1.bn];
+  if (!need_from(h, h->bns[c2.bn].rank)) {           // frozen from here on (vk_unet_set_trainable): nothing of this block runs
+    if (i > 0) h->g_prereduced[h->decs[i - 1].conv2] = 0;
+    return VK_OK;
+  }
   // conv2 unit (its gradient was pre-masked/pre-reduced by the producer when that kernel supports the fusion)
   // Order inside a unit: BN backward -> DATA gradient -> weight gradient.  The weight gradient only feeds the optimizer; issued
   // after the data gradient it can run (side stream, vk_unet_set_side_stream) beside the HBM-bound BatchNorm backward of the
   // NEXT layer instead of beside an MFMA-bound data gradient.
   RET_IF(bn_relu_bwd_inplace(h, c2, h->g_prereduced[d.conv2] != 0, st));
+  const bool into1 = need_from(h, bn1.rank);
   bool fused1 = false;
-  RET_IF(conv_dgrad_into(h, c2, c1, &fused1, st));
-  RET_IF(conv_wgrad(h, c2, to_src(bn_act(h, c1)), null_src(), st));
+  if (into1) RET_IF(conv_dgrad_into(h, c2, c1, &fused1, st));
+  if (trains(h, c2.w_t)) RET_IF(conv_wgrad(h, c2, to_src(bn_act(h, c1)), null_src(), st));
+  if (i > 0) h->g_prereduced[h->decs[i - 1].conv2] = 0;
+  if (!into1) return VK_OK;
   // conv1 unit
   RET_IF(bn_relu_bwd_inplace(h, c1, fused1, st));
   // data gradient with the nearest-x2 upsample backward fused into its epilogue (the full-resolution d_up never exists)
   // and, for i > 0, the BN+ReLU backward reduce of the previous decoder block's conv2;
   // shapes the tile kernels do not cover fall back to dgrad + a separate 2x2-sum pass
-  if (i > 0) h->g_prereduced[h->decs[i - 1].conv2] = 0;
-  {
+  if (need_from(h, c1.rank + 1)) {
     vk_conv_desc dd = dgrad_desc(h, c1);
     vk_bnr r;
     const bool want_bnr = i > 0 && !getenv("VK_NO_BNR_FUSION");
@@ -1220,6 +1300,7 @@ int backward_decoder(vk_unet* h, int i, hipStream_t st) {
       RET_IF(vk_upsample2x_bwd(h->cfg.dtype, N, d.H, d.W, d.Cup, dup, g_prev, 0, st));
     }
   }
+  if (!trains(h, c1.w_t)) return VK_OK;
   return conv_wgrad(h, c1, to_src(xprev, 1), d.Cskip ? to_src(skip) : null_src(), st);
 }
 
@@ -1230,6 +1311,10 @@ int backward_block(vk_unet* h, int bi, hipStream_t st) {
   BnL& b2 = h->bns[c2.bn];
   const vk_dtype dt = h->cfg.dtype;
   const size_t pixels = (size_t)h->cfg.N * k.Hout * k.Wout;
+  if (!need_from(h, b2.rank)) {                      // frozen from here on (vk_unet_set_trainable): nothing of this block runs
+    h->tail_prereduced[(size_t)bi] = 0;
+    return VK_OK;
+  }
   // block input (materialised) and its gradient buffer
   Act xin;
   void* gin;
@@ -1259,11 +1344,14 @@ int backward_block(vk_unet* h, int bi, hipStream_t st) {
     RET_IF(bn_bwd_phase2(h, bd, k.C, pixels, k.gout, cd.z, mm, k.out, cd.g, nullptr, 0, st));
   }
   // conv2 (data gradient first, weight gradient after it: see backward_decoder)
+  const bool into1 = need_from(h, h->bns[c1.bn].rank);
   bool fused1 = false;
-  RET_IF(conv_dgrad_into(h, c2, c1, &fused1, st));
-  RET_IF(conv_wgrad(h, c2, to_src(bn_act(h, c1)), null_src(), st));
+  if (into1) RET_IF(conv_dgrad_into(h, c2, c1, &fused1, st));
+  if (trains(h, c2.w_t)) RET_IF(conv_wgrad(h, c2, to_src(bn_act(h, c1)), null_src(), st));
+  if (!into1) return k.convd >= 0 && trains(h, h->convs[k.convd].w_t) ? conv_wgrad(h, h->convs[k.convd], to_src(xin), null_src(), st) : VK_OK;
   // conv1
   RET_IF(bn_relu_bwd_inplace(h, c1, fused1, st));
+  const bool into_gin = need_from(h, c1.rank + 1);   // some tensor of an earlier block (or the stem) is trainable
   // gin was written by the identity shortcut above or (downsample blocks) by the decoder skip gradient
   // Identity block behind another block: this data gradient COMPLETES the output gradient of block bi - 1 (gin = its gout), so its
   // epilogue applies that block's tail — mask [out > 0], sums of g and g * z2 for bn2 — while the vectors are in registers: the
@@ -1271,7 +1359,7 @@ int backward_block(vk_unet* h, int bi, hipStream_t st) {
   // batch_norm backward nodes of torchvision's BasicBlock).  Downsample blocks finish gin with their 1x1 data gradient: not fused.
   bool tail_fused = false;
   const int tail_maxc = getenv("VK_TAIL_BNR_MAXC") ? atoi(getenv("VK_TAIL_BNR_MAXC")) : 1 << 20;      // experiment knob: fuse only up to this width
-  if (k.convd < 0 && bi > 0 && c1.halo_dg && k.C <= tail_maxc && !getenv("VK_NO_TAIL_BNR_FUSION")) {
+  if (into_gin && k.convd < 0 && bi > 0 && c1.halo_dg && k.C <= tail_maxc && !getenv("VK_NO_TAIL_BNR_FUSION")) {
     BlockL& pb = h->blocks[bi - 1];
     ConvL& pc2 = h->convs[pb.conv2];
     vk_conv_desc dd = dgrad_desc(h, c1);
@@ -1281,19 +1369,20 @@ int backward_block(vk_unet* h, int bi, hipStream_t st) {
     if (rc == VK_OK) { tail_fused = true; h->tail_prereduced[(size_t)bi - 1] = 1; }
     else if (rc != VK_ERR_UNSUPPORTED) return rc;
   }
-  if (!tail_fused) RET_IF(conv_dgrad(h, c1, gin, nullptr, 0, 1, st));
+  if (into_gin && !tail_fused) RET_IF(conv_dgrad(h, c1, gin, nullptr, 0, 1, st));
   if (k.convd >= 0) {
     ConvL& cd = h->convs[k.convd];
-    RET_IF(conv_dgrad(h, cd, gin, nullptr, 0, 1, st));
-    RET_IF(conv_wgrad(h, c1, to_src(xin), null_src(), st));
-    return conv_wgrad(h, cd, to_src(xin), null_src(), st);
+    if (into_gin) RET_IF(conv_dgrad(h, cd, gin, nullptr, 0, 1, st));
+    if (trains(h, c1.w_t)) RET_IF(conv_wgrad(h, c1, to_src(xin), null_src(), st));
+    return trains(h, cd.w_t) ? conv_wgrad(h, cd, to_src(xin), null_src(), st) : VK_OK;
   }
-  return conv_wgrad(h, c1, to_src(xin), null_src(), st);
+  return trains(h, c1.w_t) ? conv_wgrad(h, c1, to_src(xin), null_src(), st) : VK_OK;
 }
 
 int backward_stem(vk_unet* h, hipStream_t st) {
   const int N = h->cfg.N, S = h->cfg.size, SW = h->cfg.width;
   ConvL& stem = h->convs[h->stem_conv];
+  if (!need_from(h, h->bns[stem.bn].rank)) return VK_OK;
   // stem.g holds the skip gradient of f1 (from decoder block 3); add the maxpool path
   if (getenv("VK_NO_POOL_BNR_FUSION")) {
     RET_IF(vk_maxpool_bwd(h->cfg.dtype, N, S / 2, SW / 2, 64, h->ws + h->off_gpool, (const uint8_t*)(h->ws + h->off_argmax), stem.g, st));
@@ -1305,8 +1394,11 @@ int backward_stem(vk_unet* h, hipStream_t st) {
                                     b.scale, b.shift, stem.g, b.bsums, st));
     // r04: the stem's dz has ONE reader, the weight gradient below (no data gradient: the input needs none) — the 16-bit kernel forms
     // dz = a*g + b*z + c itself while staging, so the apply pass (g, z -> dz: 805 MB at bs 32) is not run.  VK_NO_STEM_BNA=1: the pass
+    // A frozen stem convolution needs no dz at all: the coefficient launch alone gives the BatchNorm's gamma / beta gradients.
+    if (!trains(h, stem.w_t))
+      return vk_bn_bwd_coeffs(64, b.bsums, b.count, h->params + b.g_off, b.mean, b.invstd, dgamma_of(h, b), dbeta_of(h, b), b.coef, st);
     if (h->cfg.dtype != VK_F32 && !getenv("VK_NO_STEM_BNA")) {
-      RET_IF(vk_bn_bwd_coeffs(64, b.bsums, b.count, h->params + b.g_off, b.mean, b.invstd, h->grads + b.g_off, h->grads + b.b_off, b.coef, st));
+      RET_IF(vk_bn_bwd_coeffs(64, b.bsums, b.count, h->params + b.g_off, b.mean, b.invstd, dgamma_of(h, b), dbeta_of(h, b), b.coef, st));
       hipStream_t ws;
       RET_IF(wgrad_stream(h, st, &ws));
       const int rc = vk_stem_wgrad_bn(h->cfg.dtype, N, S, SW, h->ws + h->off_x4, stem.g, stem.z, b.coef, h->grads + stem.w_off,
@@ -1318,6 +1410,7 @@ int backward_stem(vk_unet* h, hipStream_t st) {
       RET_IF(bn_relu_bwd_inplace(h, stem, true, st));
     }
   }
+  if (!trains(h, stem.w_t)) return VK_OK;
   hipStream_t ws;
   RET_IF(wgrad_stream(h, st, &ws));
   return vk_stem_wgrad(h->cfg.dtype, N, S, SW, h->ws + h->off_x4, stem.g, h->grads + stem.w_off, h->ws + h->off_wslab, VK_WGRAD_WORKSPACE_BYTES, ws);
@@ -1343,7 +1436,7 @@ int flush_wgrads(vk_unet* h, int stage, hipStream_t st) {
   const int slot = target == 256 ? 0 : 1;
   vk_unet::WPlan& wp = h->wplans[stage][slot];
   char* const tables = h->ws + h->off_tab_wbatch + ((size_t)stage * 2 + slot) * VK_WGRAD_BATCH_TABLE_BYTES;
-  if (!wp.built || wp.target != target || wp.n != n) {
+  if (!wp.built || wp.target != target || wp.n != n || wp.version != h->mask_version) {
     if (wp.built) VK_CHECK_HIP(hipStreamSynchronize(st));          // a launch that reads the old tables may still be in flight
     vk_conv_desc descs[kMaxBatch];
     const void* dz[kMaxBatch];
@@ -1352,7 +1445,7 @@ int flush_wgrads(vk_unet* h, int stage, hipStream_t st) {
     wp.plan = vk::WgradBatchPlan();
     const int rc = vk::wgrad_batch_build(descs, dz, dw, n, target, tables, VK_WGRAD_BATCH_TABLE_BYTES, &wp.plan);
     if (rc != VK_OK) { h->pending.clear(); return rc; }
-    wp.built = true; wp.target = target; wp.n = n;
+    wp.built = true; wp.target = target; wp.n = n; wp.version = h->mask_version;
   }
   if (wp.plan.slab_need > kEngineSlabBytes) return each();
   const int rc = vk::wgrad_batch_launch(h->cfg.dtype, wp.plan, tables, slab, kEngineSlabBytes, st);
@@ -1364,17 +1457,21 @@ int backward_stage(vk_unet* h, const float* dlogits, int stage, hipStream_t st) 
   const int N = h->cfg.N, S = h->cfg.size, SW = h->cfg.width;
   switch (stage) {
     case 0: {
+      if (!need_from(h, 0)) return VK_OK;           // nothing trainable: every stage is a no-op
       VK_CHECK_HIP(hipMemsetAsync(h->ws + h->off_bsums, 0, h->stats_bytes, st));
       ConvL& last = h->convs[h->decs[4].conv2];
+      const ConvL& head = h->convs[h->head_conv];
+      float* const hdw = grad_or_sink(h, head.w_t, h->head_w_off, 1024);
+      float* const hdb = grad_or_sink(h, head.b_t, h->head_b_off, 1024 + 144);
       vk_src hs = to_src(bn_act(h, last));
       {
         vk_bnr r = bnr_of(h, last);
         const bool fuse = !getenv("VK_NO_BNR_FUSION");
         const float* dl = dlogits ? dlogits : (const float*)(h->ws + h->off_dlogits);
-        if (fuse) RET_IF(vk_head_bwd_fused(h->cfg.dtype, N, S, SW, &hs, h->params + h->head_w_off, dl, last.g, h->grads + h->head_w_off,
-                                           h->grads + h->head_b_off, &r, h->ws + h->off_wslab, VK_HEAD_WORKSPACE_BYTES, st));
-        else RET_IF(vk_head_bwd(h->cfg.dtype, N, S, SW, &hs, h->params + h->head_w_off, dl, last.g, h->grads + h->head_w_off,
-                                h->grads + h->head_b_off, h->ws + h->off_wslab, VK_HEAD_WORKSPACE_BYTES, st));
+        if (fuse) RET_IF(vk_head_bwd_fused(h->cfg.dtype, N, S, SW, &hs, h->params + h->head_w_off, dl, last.g, hdw, hdb, &r,
+                                           h->ws + h->off_wslab, VK_HEAD_WORKSPACE_BYTES, st));
+        else RET_IF(vk_head_bwd(h->cfg.dtype, N, S, SW, &hs, h->params + h->head_w_off, dl, last.g, hdw, hdb, h->ws + h->off_wslab,
+                                VK_HEAD_WORKSPACE_BYTES, st));
         h->g_prereduced[h->decs[4].conv2] = fuse ? 1 : 0;
       }
       RET_IF(backward_decoder(h, 4, st));

@@ -11,8 +11,16 @@ GradScaler (train.py:441-445, 610-611): the optimizer declares ``_step_supports_
 (``optimizer.grad_scale`` / ``optimizer.found_inf``); ``vk_adamw_step_amp`` reads both on the device,
 folds the unscale into the update, skips the whole step on an overflow and keeps its step counter on the
 device — no ``.item()``, no host round trip.  ``vk.GradScaler`` (below) additionally replaces torch's
-foreach inf check over the 140 gradient views by one pass over the flat buffer."""
+foreach inf check over the 140 gradient views by one pass over the flat buffer.
+
+Fine-tuning (frozen tensors, or an optimizer over a subset of the model's parameters): like torch, a step updates only the owned
+tensors that have a gradient, and each tensor keeps its own step count (torch's per-parameter ``state["step"]``), so a tensor that
+is unfrozen later starts its bias correction at step 1.  That is ``vk_adamw_step_amp_segments``: one segment per tensor, its tables
+built once per set of tensors.  As long as every step has covered every tensor, the whole-buffer kernel and its one counter run."""
 from __future__ import annotations
+
+import ctypes as C
+from typing import List, Optional, Tuple
 
 import torch
 
@@ -30,7 +38,8 @@ class FusedAdamW(torch.optim.Optimizer):
             raise NotImplementedError("amsgrad is not used by the reference")
         params = list(params)
         if not params or isinstance(params[0], dict):
-            raise VkError("FusedAdamW takes model.parameters() of one vickers-hardness-unet_amd.Unet (single param group)")
+            raise VkError("FusedAdamW takes model.parameters() of one vickers-hardness-unet_amd.Unet, or a subset of them "
+                          "(single param group)")
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         super().__init__(params, defaults)
         self._model = None
@@ -39,14 +48,24 @@ class FusedAdamW(torch.optim.Optimizer):
         self._scratch = None            # float32[4] device scratch of vk_adamw_step_amp
         self._pending_step = 0          # step count loaded from a state dict before the device buffers exist
         self.grad_inv_scale = 1.0       # extra factor applied to gradients inside the kernel (DP averaging)
+        # per-tensor steps (fine-tuning): int32 [tensors] on the device, created from _step_dev by the first step that leaves a tensor
+        # out; from then on every step runs the segmented kernel.  None while every step has covered every tensor.
+        self._steps_dev: Optional[torch.Tensor] = None
+        self._pending_steps: Optional[List[int]] = None     # per-tensor counts loaded from a state dict
+        self._owned: List[Tuple[int, torch.nn.Parameter]] = []   # (tensor index in the model's table, parameter)
+        self._seg_key = None            # (tensor indices, device) the segment / block tables below were built for
+        self._seg = self._blocks = self._seg_scratch = None
+        self._nblocks = 0
 
     def attach(self, model) -> "FusedAdamW":
-        """Bind to the Unet whose parameters were passed (needed to reach its flat buffers)."""
+        """Bind to the Unet whose parameters were passed (all of them or a subset; needed to reach its flat buffers)."""
         mine = {id(p) for p in self.param_groups[0]["params"]}
-        theirs = {id(p) for p in model.parameters()}
-        if mine != theirs:
-            raise VkError("FusedAdamW must own exactly the parameters of the attached model")
+        index = {id(p): i for i, p in enumerate(model._param_list)}
+        if not mine <= set(index):
+            raise VkError("FusedAdamW must own parameters of the attached model (all of them or a subset)")
         self._model = model
+        self._owned = sorted((index[id(p)], p) for p in self.param_groups[0]["params"])
+        self._seg_key = None
         return self
 
     def _find_model(self):
@@ -56,8 +75,22 @@ class FusedAdamW(torch.optim.Optimizer):
 
     @property
     def step_count(self) -> int:
-        """Optimizer steps taken so far (reads the device counter: a host sync; for logging / checkpoints only)."""
+        """Optimizer steps taken so far — with per-tensor counts the largest of them (reads the device counter: a host sync; for
+        logging / checkpoints only)."""
+        if self._steps_dev is not None:
+            return int(self._steps_dev.max().item())
+        if self._pending_steps is not None:
+            return max(self._pending_steps)
         return int(self._step_dev.item()) if self._step_dev is not None else int(self._pending_step)
+
+    def tensor_steps(self) -> List[int]:
+        """Steps taken per parameter tensor of the attached model (its table order = ``model.parameters()``; a host sync)."""
+        n = len(self._find_model()._param_list)
+        if self._steps_dev is not None:
+            return [int(v) for v in self._steps_dev.cpu()]
+        if self._pending_steps is not None:
+            return list(self._pending_steps)
+        return [self.step_count] * n
 
     def _ensure_state(self, p: torch.Tensor):
         dev = p.device
@@ -71,9 +104,17 @@ class FusedAdamW(torch.optim.Optimizer):
         if self._m.shape != p.shape:
             raise VkError("optimizer state does not match the model's flat parameter buffer")
         if self._step_dev is None or self._step_dev.device != dev:
-            start = self.step_count
+            start = self.step_count if self._steps_dev is None and self._pending_steps is None else 0
             self._step_dev = torch.full((1,), start, dtype=torch.int32, device=dev)
             self._scratch = torch.zeros(4, dtype=torch.float32, device=dev)
+        if self._pending_steps is not None:
+            if len(self._pending_steps) != len(self._find_model()._param_list):
+                raise VkError("optimizer state holds %d per-tensor steps, the model has %d tensors"
+                              % (len(self._pending_steps), len(self._find_model()._param_list)))
+            self._steps_dev = torch.tensor(self._pending_steps, dtype=torch.int32, device=dev)
+            self._pending_steps = None
+        elif self._steps_dev is not None and self._steps_dev.device != dev:
+            self._steps_dev = self._steps_dev.to(dev)
 
     @torch.no_grad()
     def zero_grad(self, set_to_none: bool = True):
@@ -88,12 +129,12 @@ class FusedAdamW(torch.optim.Optimizer):
         p, g = m.flat_params, m.flat_grads
         if not p.is_cuda:
             raise VkError("parameters are on %s: no CPU fallback" % p.device)
-        for q in self.param_groups[0]["params"]:
-            if not q.requires_grad:
-                raise VkError("FusedAdamW updates the whole flat buffer: frozen parameters (requires_grad=False) are not supported")
-        first = self.param_groups[0]["params"][0]
-        if first.grad is None:
-            raise VkError("optimizer.step() before backward(): gradients are None (zero_grad(set_to_none=True) was the last call)")
+        # torch updates the parameters that have a gradient (frozen ones have none after a backward)
+        active = tuple(t for t, q in self._owned if q.grad is not None)
+        if not active:
+            if any(q.requires_grad for _, q in self._owned):
+                raise VkError("optimizer.step() before backward(): gradients are None (zero_grad(set_to_none=True) was the last call)")
+            return None
         self._ensure_state(p)
         grp = self.param_groups[0]
         # GradScaler support: torch sets these attributes around step() (device tensors; never read on the host here)
@@ -105,6 +146,10 @@ class FusedAdamW(torch.optim.Optimizer):
             fi = fi.reshape(-1)[:1].to(device=p.device, dtype=torch.float32)
         if gs is not None:
             gs = gs.reshape(-1)[:1].to(device=p.device, dtype=torch.float32)
+        if len(active) < len(m._param_list) or self._steps_dev is not None:
+            self._step_segments(m, active, grp, gs, fi)
+            m.mark_weights_dirty()
+            return None
         check(lib().vk_adamw_step_amp(p.numel(), p.data_ptr(), g.data_ptr(), self._m.data_ptr(), self._v.data_ptr(),
                                       float(grp["lr"]), float(grp["betas"][0]), float(grp["betas"][1]), float(grp["eps"]),
                                       float(grp["weight_decay"]), self._step_dev.data_ptr(), float(self.grad_inv_scale),
@@ -113,9 +158,40 @@ class FusedAdamW(torch.optim.Optimizer):
         m.mark_weights_dirty()
         return None
 
+    def _step_segments(self, m, active: Tuple[int, ...], grp, gs, fi):
+        """vk_adamw_step_amp_segments over the tensors in `active`, one segment each, with per-tensor step counters."""
+        p, g = m.flat_params, m.flat_grads
+        dev = p.device
+        L = lib()
+        if self._steps_dev is None:        # first partial step: every tensor has taken the steps of the shared counter so far
+            self._steps_dev = self._step_dev.repeat(len(m._param_list))
+        if self._seg_key != (active, dev):    # the set of tensors changed: new tables (the only host -> device copies)
+            seg = torch.tensor([[m._param_ranges[t][0], m._param_ranges[t][0] + m._param_ranges[t][1], t] for t in active],
+                               dtype=torch.int64)
+            seg_p = C.cast(seg.data_ptr(), C.POINTER(C.c_int64))
+            nb = L.vk_adamw_segment_blocks(len(active), seg_p, None, 0)
+            if nb < 0:
+                check(nb, "vk_adamw_segment_blocks")
+            blocks = torch.empty((nb, 2), dtype=torch.int32)
+            rc = L.vk_adamw_segment_blocks(len(active), seg_p, C.cast(blocks.data_ptr(), C.POINTER(C.c_int32)), nb)
+            if rc < 0:
+                check(rc, "vk_adamw_segment_blocks")
+            self._seg, self._blocks = seg.to(dev), blocks.to(dev)
+            self._seg_scratch = torch.zeros(4 + 2 * len(active), dtype=torch.float32, device=dev)
+            self._nblocks = nb
+            self._seg_key = (active, dev)
+        check(L.vk_adamw_step_amp_segments(len(active), self._seg.data_ptr(), self._nblocks, self._blocks.data_ptr(), p.data_ptr(),
+                                           g.data_ptr(), self._m.data_ptr(), self._v.data_ptr(), float(grp["lr"]),
+                                           float(grp["betas"][0]), float(grp["betas"][1]), float(grp["eps"]), float(grp["weight_decay"]),
+                                           self._steps_dev.data_ptr(), float(self.grad_inv_scale), _lib.ptr(gs), _lib.ptr(fi),
+                                           self._seg_scratch.data_ptr(), _lib.current_stream()),
+              "vk_adamw_step_amp_segments")
+
     def state_dict(self):
         sd = super().state_dict()
         sd["fused"] = {"step": self.step_count, "exp_avg": self._m, "exp_avg_sq": self._v}
+        if self._steps_dev is not None or self._pending_steps is not None:
+            sd["fused"]["steps"] = self.tensor_steps()      # per tensor, in the model's parameter order
         return sd
 
     def load_state_dict(self, sd):
@@ -124,7 +200,10 @@ class FusedAdamW(torch.optim.Optimizer):
         super().load_state_dict(sd)
         if fused is not None:
             self._pending_step = int(fused["step"])
+            steps = fused.get("steps")      # absent in the one-counter format: "step" is then every tensor's count
+            self._pending_steps = [int(s) for s in steps] if steps is not None else None
             self._step_dev = None           # re-created on the parameters' device from _pending_step at the next step()
+            self._steps_dev = None
             self._m, self._v = fused["exp_avg"], fused["exp_avg_sq"]
 
 

@@ -23,6 +23,9 @@ streaming workgroups).
                      travel under the last stage (layer 1 + stem: HBM-bound kernels with thousands of workgroups, which lose a few
                      per cent to held CUs, not a whole round); the last, tiny bucket follows at the end;
   * ``"tail"``     — one collective over the whole buffer after the last stage (no overlap: the robust lower bound).
+Fine-tuning: a bucket that holds no trainable tensor is never reduced (its gradient range is zero on every rank, and stays rank-local);
+the "deferred" flush still fires at stage defer_until-1 when that stage's own bucket is frozen.  A partly frozen bucket is reduced whole
+(its frozen elements are zero everywhere).
 ``reserved_cus`` > 0 additionally caps the grids of the one-workgroup-per-CU weight-gradient kernels at (CUs - reserved_cus) while
 collectives are in flight (vk_set_reserved_cus).
 
@@ -92,10 +95,15 @@ class GradientReducer:
             return [(0, first)] + [(s, s + 1) for s in range(first, nbuckets)]
         return [(s, s + 1) for s in range(nbuckets)]
 
-    def bucket_ready(self, index: int, rng: Tuple[int, int]):
+    def bucket_ready(self, index: int, rng: Tuple[int, int], trainable: bool = True):
+        """Stage `index` has finished bucket `rng`; ``trainable=False``: the bucket holds no trainable tensor (nothing to reduce)."""
         if not self.enabled:
             return
         b0, b1 = rng
+        if not trainable:
+            if self.policy == "deferred" and index >= self.defer_until - 1 and self._held:
+                self._flush_held()
+            return
         if b1 <= b0:
             return
         if self.policy == "eager":

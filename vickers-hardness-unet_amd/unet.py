@@ -50,6 +50,8 @@ class _Plan:
         self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
         self.loss_out = torch.zeros(4, dtype=torch.float32, device=dev)
         self.weights_version = None
+        self.mask = None                    # trainable flags the engine holds (vk_unet_set_trainable); None: not pushed yet
+        self.bucket_trainable: List[bool] = []
         self.nbuckets = L.vk_unet_num_buckets(h)
         self.buckets: List[Tuple[int, int]] = []
         for b in range(self.nbuckets):
@@ -64,6 +66,16 @@ class _Plan:
         check(lib().vk_unet_bind(self.h, f["params"].data_ptr(), _lib.ptr(grads), f["bufs"].data_ptr(),
                                  f["nbt"].data_ptr(), self.ws.data_ptr(), self.ws_bytes), "vk_unet_bind")
         self.weights_version = None
+
+    def set_trainable(self, model: "Unet", mask: Tuple[bool, ...]):
+        """Hand the engine one requires_grad flag per parameter tensor (host only; done when the flags change)."""
+        if mask == self.mask:
+            return
+        flags = (C.c_uint8 * len(mask))(*mask)
+        check(lib().vk_unet_set_trainable(self.h, flags, len(mask)), "vk_unet_set_trainable")
+        self.mask = mask
+        ranges = [(off, off + numel) for (off, numel), t in zip(model._param_ranges, mask) if t]
+        self.bucket_trainable = [any(a < b1 and b0 < b for a, b in ranges) for b0, b1 in self.buckets]
 
     def debug_tensor(self, name: str) -> torch.Tensor:
         """Copy of a named intermediate (NHWC) — parity/debug only."""
@@ -91,14 +103,14 @@ class _Plan:
 
 class _UnetFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, anchor, model, plan):
-        ctx.model, ctx.plan = model, plan
+    def forward(ctx, x, anchor, model, plan, mask):
+        ctx.model, ctx.plan, ctx.mask = model, plan, mask      # requires_grad as it was when the forward ran (torch records it then)
         return model._run_forward(plan, x, True)
 
     @staticmethod
     def backward(ctx, g):
-        ctx.model._run_backward(ctx.plan, g.contiguous().float())
-        return None, None, None, None
+        ctx.model._run_backward(ctx.plan, g.contiguous().float(), ctx.mask)
+        return None, None, None, None, None
 
 
 class Unet(nn.Module):
@@ -189,6 +201,7 @@ class Unet(nn.Module):
                 mod._buffers[leaf] = v
         self._anchor = torch.zeros((), requires_grad=True, device=self._flat["params"].device)
         self._param_list = [self._leaves[t[0]][0]._parameters[self._leaves[t[0]][1]] for t in self._table if t[1] in (0, 1)]
+        self._param_ranges = [(t[3], t[4]) for t in self._table if t[1] in (0, 1)]
 
     def _apply(self, fn, recurse=True):
         for k in ("params", "grads", "bufs", "nbt"):
@@ -274,12 +287,28 @@ class Unet(nn.Module):
             self._flat["grads"] = torch.zeros_like(self._flat["params"])
         return self._flat["grads"]
 
-    def _attach_grads(self):
+    def _attach_grads(self, mask: Optional[Tuple[bool, ...]] = None, missing_only: bool = False):
+        """Point ``.grad`` of the trainable parameters at their views of the flat gradient buffer; frozen ones get None (torch leaves the
+        grad of a parameter that did not require it untouched: with ``missing_only`` they keep theirs, and a trainable tensor that had
+        none starts from zero, as a fresh torch grad does)."""
         g = self._ensure_grads()
+        i = 0
         for name, kind, dims, off, numel in self._table:
             if kind in (0, 1):
                 mod, leaf = self._leaves[name]
-                mod._parameters[leaf].grad = self._view(kind, dims, off, numel, "grads")
+                p = mod._parameters[leaf]
+                if mask is None or mask[i]:
+                    if not missing_only or p.grad is None:
+                        view = self._view(kind, dims, off, numel, "grads")
+                        if missing_only:
+                            view.zero_()
+                        p.grad = view
+                elif not missing_only:
+                    p.grad = None
+                i += 1
+
+    def _trainable_mask(self) -> Tuple[bool, ...]:
+        return tuple(bool(p.requires_grad) for p in self._param_list)
 
     def mark_weights_dirty(self):
         """Call after writing the flat parameter buffer through a raw pointer (FusedAdamW does)."""
@@ -325,13 +354,22 @@ class Unet(nn.Module):
         plan._last_x = x      # keep the input alive until backward has consumed the plan's x4 copy
         return logits
 
-    def _run_backward(self, plan: _Plan, dlogits: Optional[torch.Tensor]):
+    def _run_backward(self, plan: _Plan, dlogits: Optional[torch.Tensor], mask: Tuple[bool, ...]):
         L = lib()
         st = _lib.current_stream()
-        first = next(iter(self.parameters()))
-        if first.grad is None:
+        plan.set_trainable(self, mask)
+        if all(mask):
+            fresh = next(iter(self.parameters())).grad is None
+        else:
+            # fine-tuning: the buffer is zeroed when no trainable tensor holds a gradient (after zero_grad; not from a fixed tensor —
+            # the stem weight, say, when it is frozen, or a tensor unfrozen between two accumulating backwards); frozen ranges stay 0
+            fresh = all(p.grad is None for p, t in zip(self._param_list, mask) if t)
+        if fresh:
             check(L.vk_unet_zero_grad(plan.h, st), "vk_unet_zero_grad")
-            self._attach_grads()
+            self._attach_grads(None if all(mask) else mask)
+        else:
+            # accumulating: a trainable tensor whose grad was set to None (an optimizer over a subset zeroes only its own) starts at 0
+            self._attach_grads(mask, missing_only=True)
         red = self._reducer
         if red is not None and getattr(red, "enabled", True) and not getattr(plan, "_side_off", False):
             check(L.vk_unet_set_side_stream(plan.h, 0), "vk_unet_set_side_stream")    # see include/vk_unet.h
@@ -367,7 +405,10 @@ class Unet(nn.Module):
                     self._group_events.append((s0, s1, e0, e1))
                 if red is not None:
                     for s in range(s0, s1):
-                        red.bucket_ready(s, plan.buckets[s])
+                        if plan.bucket_trainable[s]:
+                            red.bucket_ready(s, plan.buckets[s])
+                        else:
+                            red.bucket_ready(s, plan.buckets[s], trainable=False)    # frozen: no collective (parallel.py)
         finally:
             if capped:
                 L.vk_set_reserved_cus(0)
@@ -391,10 +432,11 @@ class Unet(nn.Module):
             dtype = torch.get_autocast_dtype('cuda')
         else:
             dtype = self.compute_dtype
-        need_grad = self.training and torch.is_grad_enabled()
+        mask = self._trainable_mask()
+        need_grad = self.training and torch.is_grad_enabled() and any(mask)    # nothing trainable: a plain train-mode forward, as torch
         plan = self.plan_for(N, S, dtype, need_grad or self.training)
         if need_grad:
-            return _UnetFn.apply(x, self._anchor, self, plan)
+            return _UnetFn.apply(x, self._anchor, self, plan, mask)
         return self._run_forward(plan, x, self.training)
 
     # ------------------------------------------------------------------ fused step (no autograd graph)
@@ -402,15 +444,19 @@ class Unet(nn.Module):
                           dtype: Optional[torch.dtype] = None) -> torch.Tensor:
         """forward (batch-stat BN) + BCE+Dice + backward in one call; the engine's loss kernel feeds the
         head gradient directly.  Returns a device tensor [total, bce, dice] (no host sync).
-        Equivalent to train.py:436-448 ``logits = model(x); loss = bce + dice; loss.backward()``."""
+        Equivalent to train.py:436-448 ``logits = model(x); loss = bce + dice; loss.backward()``; ``requires_grad`` of the parameters
+        is read at this call (frozen ones get no gradient, see INTEGRATION.md "Fine-tuning")."""
         self._check_input(x)
+        mask = self._trainable_mask()
+        if not any(mask):
+            raise VkError("loss_and_backward: no parameter requires grad (every tensor is frozen)")
         N, _, H, W = x.shape
         plan = self.plan_for(N, H if H == W else (H, W), dtype or self.compute_dtype, True)
         logits = self._run_forward(plan, x, True)
         y = y.detach().contiguous().float()
         check(lib().vk_unet_loss(plan.h, logits.data_ptr(), y.data_ptr(), plan.loss_out.data_ptr(), float(grad_scale),
                                  1.0, 1.0, _lib.current_stream()), "vk_unet_loss")
-        self._run_backward(plan, None)
+        self._run_backward(plan, None, mask)
         self.last_logits = logits
         return plan.loss_out[:3]
 

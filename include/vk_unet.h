@@ -10,6 +10,8 @@
  *   vk_unet_loss .............................. bce(logits,y)+dice(logits,y) train.py:438, 513 (600-601)
  *   vk_unet_backward .......................... loss.backward()              train.py:443, 448
  *   vk_unet_set_trainable ..................... p.requires_grad_(False) before backward (fine-tuning with a frozen encoder)
+ *   vk_unet_set_bn_frozen ..................... module.eval() of single BatchNorm layers inside a training forward
+ *   vk_unet_set_input_grad .................... x.requires_grad_() (x.grad: saliency maps)
  *   vk_seg_metrics ............................ dice_coef / iou_coef (validate) train.py:230-281, 518-522
  *   vk_comm_* / vk_allreduce_bucket ........... (no reference counterpart: the 8-GPU data-parallel exchange)
  *   vk_adamw_step ............................. optimizer.step()/zero_grad   train.py:428, 449 (606)
@@ -204,6 +206,12 @@ int vk_stem_wgrad(vk_dtype dtype, int N, int H, int W, const void* x4, const voi
  * train.py:448 -> encoder.bn1) disappears. */
 int vk_stem_wgrad_bn(vk_dtype dtype, int N, int H, int W, const void* x4, const void* g, const void* z, const float* coef_abc,
                      float* dw_krsc3, void* workspace, size_t workspace_bytes, void* stream);
+/* Data gradient of the stem, i.e. the gradient of the model's input: dx fp32 NCHW [N][3][H][W] is WRITTEN (not accumulated) from
+ * dz [N][H/2][W/2][64] (activation dtype) and the fp32 KRSC stem weight w [64][7][7][3].  coef_abc NULL: g is dz.  Otherwise g is the
+ * masked upstream gradient, z the stem convolution's output and coef_abc = [3][64] (vk_bn_bwd_coeffs / _frozen): the kernel forms
+ * dz = a*g + b*z + c while it loads its operand.  H % 8 == 0, W % 32 == 0. */
+int vk_stem_dgrad(vk_dtype dtype, int N, int H, int W, const void* g, const void* z, const float* coef_abc, const float* w_krsc3,
+                  float* dx, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * The steps either side of model(x) in the inference wrappers, one fused pass each.
@@ -362,6 +370,10 @@ int vk_bn_bwd_coeffs(int C, const double* sums, double count, const float* gamma
 int vk_bn_bwd_apply(vk_dtype dtype, size_t pixels, int C, const void* dy, const void* z, int mask_mode,
                     const float* scale, const float* shift, const void* mask_src, const float* coef_abc, void* dz,
                     void* g_out, int g_accumulate, void* stream);
+/* phase 1.5 of a BatchNorm with FROZEN statistics (eval-mode layer in a training forward): running_mean / running_invstd are what the
+ * forward normalised with (1/sqrt(running_var + eps)).  dgamma += r * sum g*(z - mean), dbeta += sum g;  coef_abc = (gamma*r, 0, 0). */
+int vk_bn_bwd_coeffs_frozen(int C, const double* sums, const float* gamma, const float* running_mean, const float* running_invstd,
+                            float* dgamma, float* dbeta, float* coef_abc, void* stream);
 /* phase 2 with vk_bn_bwd_coeffs folded in: coefficients are derived from `sums` inside the kernel and
  * dgamma/dbeta are accumulated by it (one launch less per BatchNorm layer). */
 int vk_bn_bwd_apply_fused(vk_dtype dtype, size_t pixels, int C, const void* dy, const void* z, int mask_mode,
@@ -508,13 +520,24 @@ int vk_unet_loss(vk_unet* h, const float* logits, const float* target, float* lo
  * Only the gradients of TRAINABLE tensors (vk_unet_set_trainable) are written; the element ranges of frozen tensors are left
  * untouched, so after a zeroing they stay exactly zero.  A launch runs only if something it writes is needed: a weight or
  * gamma / beta gradient iff its tensor is trainable, a data gradient or BatchNorm-backward pass iff a trainable tensor lies at or
- * behind it in the backward order (head, decoder blocks 4..0, encoder blocks layer4.2 .. layer1.0, stem).  Stages behind the last
- * trainable tensor are no-ops that return VK_OK. */
+ * behind it in the backward order (head, decoder blocks 4..0, encoder blocks layer4.2 .. layer1.0, stem, and last the input when
+ * vk_unet_set_input_grad gave it a buffer).  Stages behind the last trainable tensor are no-ops that return VK_OK.  BatchNorm layers
+ * run in the modes of the training forward before (vk_unet_set_bn_frozen): a frozen layer's gamma / beta gradient needs its
+ * reduction only when gamma or beta is trainable; its dz = gamma / sqrt(running_var + eps) * g never does. */
 int vk_unet_backward(vk_unet* h, const float* dlogits, int stage_begin, int stage_end, void* stream);
 /* Fine-tuning: one flag per parameter tensor (kinds 0 and 1 of vk_unet_tensor_info, in table order; nonzero = trainable, i.e.
  * torch's requires_grad).  n must be the number of parameter tensors (140), else VK_ERR_ARG.  Host-only; takes effect at the next
  * vk_unet_backward.  A new plan starts with every tensor trainable, which is the unpruned schedule. */
 int vk_unet_set_trainable(vk_unet* h, const uint8_t* flags, int n);
+/* Per-layer BatchNorm modes: one flag per BatchNorm layer (46, in the order of the num_batches_tracked entries of the tensor table;
+ * nonzero = frozen statistics, torch's eval() of that module), else VK_ERR_ARG.  Host-only; takes effect at the next TRAINING
+ * forward, which normalises a frozen layer with its running statistics, leaves its running_mean / running_var /
+ * num_batches_tracked untouched and records the modes for the backward that follows it.  Eval forwards (training = 0) are unchanged. */
+int vk_unet_set_bn_frozen(vk_unet* h, const uint8_t* flags, int n);
+/* Gradient of the input: dx fp32 NCHW [N][3][H][W] (or NULL: none, the default).  When set, vk_unet_backward's last stage WRITES dx
+ * (the input ranks behind the stem in the pruning order, so every data gradient down to the stem runs even with every parameter
+ * frozen).  Host-only. */
+int vk_unet_set_input_grad(vk_unet* h, float* dx);
 int vk_unet_zero_grad(vk_unet* h, void* stream);
 
 /* ------------------------------------------------------------------------------------------------

@@ -101,6 +101,7 @@ SIGNATURES = {
     "vk_conv_wgrad_batch": (ci, [P(vk_conv_desc), P(vp), P(vp), ci, ci, vp, sz, vp, sz, vp]),
     "vk_stem_wgrad": (ci, [ci, ci, ci, ci, vp, vp, vp, vp, sz, vp]),
     "vk_stem_wgrad_bn": (ci, [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "vk_stem_dgrad": (ci, [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]),
     "vk_letterbox_preprocess": (ci, [P(vk_letterbox_desc), vp, vp, vp]),
     "vk_letterbox_postprocess_mask": (ci, [P(vk_letterbox_desc), vp, cf, vp, vp]),
     "vk_letterbox_postprocess_prob": (ci, [P(vk_letterbox_desc), vp, vp, vp]),
@@ -119,6 +120,7 @@ SIGNATURES = {
     "vk_bn_add_relu": (ci, [ci, sz, ci, vp, vp, vp, vp, vp, vp, vp, vp]),
     "vk_bn_bwd_reduce": (ci, [ci, sz, ci, vp, vp, ci, vp, vp, vp, vp, vp]),
     "vk_bn_bwd_coeffs": (ci, [ci, vp, cd, vp, vp, vp, vp, vp, vp, vp]),
+    "vk_bn_bwd_coeffs_frozen": (ci, [ci, vp, vp, vp, vp, vp, vp, vp, vp]),
     "vk_bn_bwd_apply": (ci, [ci, sz, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, ci, vp]),
     "vk_bn_bwd_apply_fused": (ci, [ci, sz, ci, vp, vp, ci, vp, vp, vp, vp, cd, vp, vp, vp, vp, vp, vp, vp, ci, vp]),
     "vk_upsample2x_bwd": (ci, [ci, ci, ci, ci, ci, vp, vp, ci, vp]),
@@ -150,6 +152,8 @@ SIGNATURES = {
     "vk_unet_loss": (ci, [vp, vp, vp, vp, cf, cf, cf, vp]),
     "vk_unet_backward": (ci, [vp, vp, ci, ci, vp]),
     "vk_unet_set_trainable": (ci, [vp, P(C.c_uint8), ci]),
+    "vk_unet_set_bn_frozen": (ci, [vp, P(C.c_uint8), ci]),
+    "vk_unet_set_input_grad": (ci, [vp, vp]),
     "vk_unet_zero_grad": (ci, [vp, vp]),
     "vk_unet_debug_tensor": (ci, [vp, C.c_char_p, P(vp), P(ci * 4)]),
     "vk_comm_unique_id": (ci, [vp]),

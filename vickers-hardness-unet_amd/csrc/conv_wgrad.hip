@@ -656,7 +656,138 @@ int stem_wgrad_impl(vk_dtype dt, int N, int H, int W, const void* x4, const void
   return VK_ERR_ARG;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Data gradient of the stem (the gradient of the model's input): the transpose of the 7x7 stride-2 pad-3 convolution, 64 -> 3
+// channels, in the space-to-depth form.  Output pixel (2i + u, 2j + v) receives dz[i - 1 + wy][j - 1 + wx][k] * w[k][r][s][c] with
+// r = u + 5 - 2 wy, s = v + 5 - 2 wx (a tap exists where 0 <= r, s <= 6: 3 rows for u = 0, 4 for u = 1), so every 2x2 output block
+// (i, j) reads the same 4x4 window of dz.  One GEMM:  M = N * Ho * Wo blocks, K = 16 window positions x 64 channels, N = 12 outputs
+// (u, v, c) padded to 16, against a re-packed weight matrix of which 49 / 64 taps are non-zero.
+//   A (dz): lane (m = lane & 15, q = lane >> 4) holds block j0 + m, channels grp * 4 VE + q VE .. + VE - 1 of one window position:
+//           ONE 16-byte NHWC load per lane and MFMA step (16-bit: one 16x16x32; fp32: four 16x16x4, Mma<float>'s k permutation);
+//   B (weights): the same (window, group, lane) geometry, built once per workgroup in LDS from the fp32 KRSC master weights;
+//   D: lane holds output (u, v, c) = lane & 15 of blocks j0 + 4q .. 4q + 3.
+// BNA: dz = a*g + b*z + c is formed while loading (k_bn_bwd_apply's fp32 expression), zero outside the image: no dz pass.
+// Workgroup: 4 waves on block rows 4 ty .. 4 ty + 3 of one 16-block column strip (their windows overlap: L1 / L2 reuse).
+struct StemDgParams {
+  const void* g;
+  const void* z;
+  const float* coef;      // [3][64] (BNA)
+  const float* w;         // fp32 KRSC [64][7][7][3]
+  float* dx;              // fp32 NCHW [N][3][H][W]
+  int N, H, W, Ho, Wo, tiles_x, tiles_y, ntiles;
+};
+
+template <typename T, bool BNA>
+__global__ __launch_bounds__(256) void k_stem_dgrad(const StemDgParams p) {
+  constexpr int VE = ElemTraits<T>::kVec;
+  constexpr int CPG = 4 * VE;            // channels per MFMA step: 32 (16-bit), 16 (fp32)
+  constexpr int NG = 64 / CPG;
+  __shared__ u32x4_t Bs[16 * NG * 64];   // [window][group][lane]: 32 KB (16-bit) / 64 KB (fp32)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int m = lane & 15, q = lane >> 4;
+  for (int sl = tid; sl < 16 * NG * 64; sl += 256) {
+    const int ln = sl & 63, grp = (sl >> 6) % NG, win = sl / (64 * NG);
+    const int n = ln & 15, wy = win >> 2, wx = win & 3;
+    const int uv = n / 3, c = n - 3 * uv;
+    const int r = (uv >> 1) + 5 - 2 * wy, s = (uv & 1) + 5 - 2 * wx;
+    const bool tap = n < 12 && r >= 0 && r <= 6 && s >= 0 && s <= 6;
+    float f[VE];
+#pragma unroll
+    for (int j = 0; j < VE; ++j) {
+      const int k = grp * CPG + (ln >> 4) * VE + j;
+      f[j] = tap ? p.w[((k * 7 + r) * 7 + s) * 3 + c] : 0.f;
+    }
+    Bs[sl] = Vec16<T>::pack(f);
+  }
+  float ca[NG][VE], cb[NG][VE], cc[NG][VE];
+  if (BNA) {
+#pragma unroll
+    for (int grp = 0; grp < NG; ++grp)
+#pragma unroll
+      for (int j = 0; j < VE; ++j) {
+        const int k = grp * CPG + q * VE + j;
+        ca[grp][j] = p.coef[k];
+        cb[grp][j] = p.coef[64 + k];
+        cc[grp][j] = p.coef[128 + k];
+      }
+  }
+  __syncthreads();
+  const T* g = (const T*)p.g;
+  const T* z = (const T*)p.z;
+  for (int t = blockIdx.x; t < p.ntiles; t += gridDim.x) {
+    const int tx = t % p.tiles_x, ty = (t / p.tiles_x) % p.tiles_y, nimg = t / (p.tiles_x * p.tiles_y);
+    const int i = ty * 4 + wave, j0 = tx * 16;
+    f32x4_t acc = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+    for (int wy = 0; wy < 4; ++wy) {
+      const int oy = i - 1 + wy;
+      const bool row_ok = oy >= 0 && oy < p.Ho;
+#pragma unroll
+      for (int wx = 0; wx < 4; ++wx) {
+        const int ox = j0 + m - 1 + wx;
+        const bool ok = row_ok && ox >= 0 && ox < p.Wo;
+        const size_t pix = ((size_t)nimg * p.Ho + (ok ? oy : 0)) * p.Wo + (ok ? ox : 0);
+#pragma unroll
+        for (int grp = 0; grp < NG; ++grp) {
+          const size_t e = pix * 64 + grp * CPG + q * VE;
+          u32x4_t a = u32x4_t{0, 0, 0, 0};
+          if (ok) {
+            a = *reinterpret_cast<const u32x4_t*>(g + e);
+            if (BNA) {
+              float gf[VE], zf[VE], o[VE];
+              Vec16<T>::unpack(a, gf);
+              Vec16<T>::unpack(*reinterpret_cast<const u32x4_t*>(z + e), zf);
+#pragma unroll
+              for (int jj = 0; jj < VE; ++jj) o[jj] = fmaf(ca[grp][jj], gf[jj], fmaf(cb[grp][jj], zf[jj], cc[grp][jj]));
+              a = Vec16<T>::pack(o);
+            }
+          }
+          acc = Mma<T>::run(a, Bs[((wy * 4 + wx) * NG + grp) * 64 + lane], acc);
+        }
+      }
+    }
+    if (m < 12) {
+      const int uv = m / 3, c = m - 3 * uv;
+      float* dst = p.dx + (((size_t)nimg * 3 + c) * p.H + 2 * i + (uv >> 1)) * p.W + (uv & 1);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) dst[2 * (j0 + 4 * q + e)] = acc[e];
+    }
+  }
+}
+
+static int stem_dgrad_impl(vk_dtype dt, int N, int H, int W, const void* g, const void* z, const float* coef, const float* w, float* dx,
+                           hipStream_t st) {
+  VK_CHECK_ARG(g && w && dx && (!coef || z), "vk_stem_dgrad: null argument");
+  VK_CHECK_ARG(N >= 1 && H >= 8 && W >= 32 && H % 8 == 0 && W % 32 == 0, "vk_stem_dgrad: H=%d W=%d (need H %% 8 == 0, W %% 32 == 0)", H, W);
+  VK_CHECK_ARG(dt == VK_F32 || dt == VK_BF16 || dt == VK_F16, "vk_stem_dgrad: bad dtype");
+  StemDgParams q;
+  q.g = g; q.z = z; q.coef = coef; q.w = w; q.dx = dx;
+  q.N = N; q.H = H; q.W = W; q.Ho = H / 2; q.Wo = W / 2;
+  q.tiles_x = q.Wo / 16; q.tiles_y = q.Ho / 4;
+  q.ntiles = N * q.tiles_x * q.tiles_y;
+  const int cap = dt == VK_F32 ? 512 : 1024;            // persistent: every workgroup builds the weight table once
+  const int nb = q.ntiles < cap ? q.ntiles : cap;
+  const double eb = dt == VK_F32 ? 4.0 : 2.0;
+  static const std::string tag = "stem_dgrad", tag_bn = "stem_dgrad_bn";
+  vkh::ProfScope ps(coef ? tag_bn.c_str() : tag.c_str(), st, 2.0 * (double)N * q.Ho * q.Wo * 1024.0 * 16.0,
+                    (double)N * q.Ho * q.Wo * 64 * eb * (coef ? 2.0 : 1.0) + (double)N * 3 * H * W * 4.0);
+#define VK_SDG(TT, B) hipLaunchKernelGGL((k_stem_dgrad<TT, B>), dim3((unsigned)nb), dim3(256), 0, st, q)
+  switch (dt) {
+    case VK_F32: if (coef) VK_SDG(float, true); else VK_SDG(float, false); break;
+    case VK_BF16: if (coef) VK_SDG(bf16_t, true); else VK_SDG(bf16_t, false); break;
+    case VK_F16: if (coef) VK_SDG(f16_t, true); else VK_SDG(f16_t, false); break;
+  }
+#undef VK_SDG
+  VK_CHECK_HIP(hipGetLastError());
+  return VK_OK;
+}
+
 }  // namespace vk
+
+extern "C" int vk_stem_dgrad(vk_dtype dtype, int N, int H, int W, const void* g, const void* z, const float* coef_abc, const float* w_krsc3,
+                             float* dx, void* stream) {
+  return vk::stem_dgrad_impl(dtype, N, H, W, g, z, coef_abc, w_krsc3, dx, (hipStream_t)stream);
+}
 
 extern "C" int vk_conv_wgrad(const vk_conv_desc* d, const void* dz, float* dw, void* workspace, size_t workspace_bytes, void* stream) {
   return vk::conv_wgrad_impl(d, dz, dw, workspace, workspace_bytes, (hipStream_t)stream);

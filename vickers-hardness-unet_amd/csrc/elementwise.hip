@@ -464,6 +464,33 @@ __global__ __launch_bounds__(256) void k_bn_bwd_coeffs(int C, const double* __re
   coef[2 * C + c] = (float)cc;
 }
 
+// Frozen statistics (an eval-mode BatchNorm inside a training forward): the layer normalised with its running mean / variance, which
+// do not depend on the batch, so dz = a*g with a = gamma*r and the sums only feed dgamma = r*(S_gz - mu*S_g), dbeta = S_g (mu, r: the
+// running mean and 1/sqrt(running_var + eps), in save_mean / save_invstd).  coef = (a, 0, 0), a as the forward's fp32 scale.
+__global__ __launch_bounds__(256) void k_bn_bwd_coeffs_frozen(int C, const double* __restrict__ sums, const float* __restrict__ gamma,
+                                                              const float* __restrict__ save_mean, const float* __restrict__ save_invstd,
+                                                              float* dgamma, float* dbeta, float* coef) {
+  const int c = blockIdx.x * 8 + (threadIdx.x >> 5);
+  const int q = threadIdx.x & 31;
+  double sg = 0.0, sgz = 0.0;
+  if (c < C) {
+    sg = sums[(size_t)q * 2 * C + c];
+    sgz = sums[(size_t)q * 2 * C + C + c];
+  }
+#pragma unroll
+  for (int o = 16; o > 0; o >>= 1) {
+    sg += __shfl_xor(sg, o, 64);
+    sgz += __shfl_xor(sgz, o, 64);
+  }
+  if (q != 0 || c >= C) return;
+  const float r = save_invstd[c];
+  dgamma[c] += (float)((double)r * (sgz - (double)save_mean[c] * sg));
+  dbeta[c] += (float)sg;
+  coef[c] = gamma[c] * r;
+  coef[C + c] = 0.f;
+  coef[2 * C + c] = 0.f;
+}
+
 // dz = a*g + b*z + c with (a, b, c) derived in-kernel from the reduction sums:
 //   dgamma = r*(S_gz - mu*S_g), dbeta = S_g, a = gamma*r, b = -gamma*r^2*dgamma/M, c = -a*dbeta/M - b*mu
 // Workgroup 0 also accumulates dgamma/dbeta into the flat gradient buffer (coef == nullptr: fused mode).
@@ -1428,6 +1455,16 @@ extern "C" int vk_bn_bwd_coeffs(int C, const double* sums, double count, const f
   vkh::ProfScope ps_("bn_bwd_coeffs", (hipStream_t)stream, 0.0, (double)C * 48.0);
   hipLaunchKernelGGL(k_bn_bwd_coeffs, dim3((C + 7) / 8), dim3(256), 0, (hipStream_t)stream, C, sums, count, gamma, save_mean,
                      save_invstd, dgamma, dbeta, coef_abc);
+  VK_CHECK_HIP(hipGetLastError());
+  return VK_OK;
+}
+
+extern "C" int vk_bn_bwd_coeffs_frozen(int C, const double* sums, const float* gamma, const float* running_mean, const float* running_invstd,
+                                       float* dgamma, float* dbeta, float* coef_abc, void* stream) {
+  VK_CHECK_ARG(sums && gamma && running_mean && running_invstd && dgamma && dbeta && coef_abc, "vk_bn_bwd_coeffs_frozen: null argument");
+  vkh::ProfScope ps_("bn_bwd_coeffs_frozen", (hipStream_t)stream, 0.0, (double)C * 48.0);
+  hipLaunchKernelGGL(k_bn_bwd_coeffs_frozen, dim3((C + 7) / 8), dim3(256), 0, (hipStream_t)stream, C, sums, gamma, running_mean,
+                     running_invstd, dgamma, dbeta, coef_abc);
   VK_CHECK_HIP(hipGetLastError());
   return VK_OK;
 }

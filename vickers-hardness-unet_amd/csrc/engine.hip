@@ -307,6 +307,33 @@ __global__ void k_inc_i64(int n, int64_t* p) {
   if (i < n) p[i] += 1;
 }
 
+// training forward with per-layer BatchNorm modes (vk_unet_set_bn_frozen): num_batches_tracked of the train-mode layers only
+__global__ void k_inc_i64_masked(int n, int64_t* p, uint64_t frozen) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n && !((frozen >> i) & 1ull)) p[i] += 1;
+}
+
+// the frozen-statistics layers of a training forward (bit e of `frozen`: layer e): the eval affine exactly as k_bn_eval_all forms it,
+// mean / invstd = the running values (what the backward's dgamma reads) and the backward coefficients (a, b, c) = (scale, 0, 0) — dz
+// of a layer that normalised with constants does not depend on the batch.  One workgroup per layer; the others return at once.
+__global__ void k_bn_frozen_affine(const BnEvalEntry* __restrict__ tab, uint64_t frozen, const float* __restrict__ params,
+                                   const float* __restrict__ bufs, float* __restrict__ arena, float eps) {
+  if (!((frozen >> blockIdx.x) & 1ull)) return;
+  const BnEvalEntry e = tab[blockIdx.x];
+  float* f = arena + e.out_off;
+  for (int c = threadIdx.x; c < e.C; c += blockDim.x) {
+    const float invstd = (float)(1.0 / sqrt((double)bufs[e.rv_off + c] + (double)eps));
+    const float sc = params[e.g_off + c] * invstd;
+    f[c] = sc;
+    f[e.C + c] = params[e.b_off + c] - bufs[e.rm_off + c] * sc;
+    f[2 * e.C + c] = bufs[e.rm_off + c];
+    f[3 * e.C + c] = invstd;
+    f[4 * e.C + c] = sc;
+    f[5 * e.C + c] = 0.f;
+    f[6 * e.C + c] = 0.f;
+  }
+}
+
 // ---------------------------------------------------------------- plan structures
 struct ConvL {
   std::string name;       // state-dict prefix; weight key = name + ".weight"
@@ -384,6 +411,11 @@ struct vk_unet {
   // or behind it in the backward order (ranks: assign_backward_ranks).  All trainable (the default) is the unpruned schedule.
   std::vector<uint8_t> trainable;
   int last_rank = 0;             // highest rank of a trainable tensor; -1: none
+  // BatchNorm modes (vk_unet_set_bn_frozen): bit l = layer l normalises with its running statistics.  `bn_frozen` is what the caller
+  // asked for; a training forward copies it to `bn_frozen_fwd`, which the backward after it reads (the modes the forward ran with)
+  uint64_t bn_frozen = 0, bn_frozen_fwd = 0;
+  float* dx_in = nullptr;        // vk_unet_set_input_grad: fp32 NCHW gradient of the input, written by the last backward stage
+  int input_rank = 0;            // the input's position in the backward order: behind the stem
   unsigned mask_version = 0;     // bumped by every change of `trainable` (keys the batched weight-gradient tables)
   std::vector<ConvL> convs;
   std::vector<BnL> bns;
@@ -451,6 +483,10 @@ size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 // gradient slot of a frozen gamma / beta / head tensor is the never-read sink, so its range of the flat buffer stays exactly zero
 bool need_from(const vk_unet* h, int rank) { return h->last_rank >= rank; }
 bool trains(const vk_unet* h, int t) { return h->trainable[(size_t)t] != 0; }
+// per-layer BatchNorm mode of the last training forward, and whether the layer's backward reduction (sum g, sum g*z) has a reader:
+// a train-mode layer's dz needs it, a frozen layer's only its gamma / beta gradient
+bool frozen(const vk_unet* h, const BnL& b) { return (h->bn_frozen_fwd >> b.idx) & 1ull; }
+bool bn_sums_needed(const vk_unet* h, const BnL& b) { return !frozen(h, b) || trains(h, b.g_t) || trains(h, b.b_t); }
 float* grad_or_sink(vk_unet* h, int t, int64_t off, int sink_off) {
   return trains(h, t) ? h->grads + off : (float*)(h->ws + h->off_gscratch) + sink_off;
 }
@@ -621,8 +657,20 @@ void assign_backward_ranks(vk_unet* h) {
     bn(k.conv1); conv(k.conv1);
   }
   bn(h->stem_conv); conv(h->stem_conv);
+  h->input_rank = r;
   h->trainable.assign((size_t)h->n_ptensors, 1);
   h->last_rank = r - 1;
+}
+
+void update_last_rank(vk_unet* h) {
+  h->last_rank = -1;
+  for (const ConvL& c : h->convs) {
+    if (trains(h, c.w_t) || (c.b_t >= 0 && trains(h, c.b_t))) h->last_rank = std::max(h->last_rank, c.rank);
+  }
+  for (const BnL& b : h->bns) {
+    if (trains(h, b.g_t) || trains(h, b.b_t)) h->last_rank = std::max(h->last_rank, b.rank);
+  }
+  if (h->dx_in) h->last_rank = h->input_rank;
 }
 
 void layout_workspace(vk_unet* h) {
@@ -778,7 +826,7 @@ Act bn_act(const vk_unet* h, const ConvL& c) {   // relu(bn(z)) as a virtual ten
   } while (0)
 
 int finalize_bn(vk_unet* h, BnL& b, int training, hipStream_t st) {
-  if (!training) return VK_OK;   // eval affine was produced for all layers at the start of forward
+  if (!training || frozen(h, b)) return VK_OK;   // eval affine was produced at the start of forward (all layers / the frozen ones)
   return vk_bn_finalize(b.C, 1, b.stats, b.count, h->params + b.g_off, h->params + b.b_off, h->bufs + b.rm_off,
                         h->bufs + b.rv_off, 1e-5f, 0.1f, b.scale, b.shift, b.mean, b.invstd, st);
 }
@@ -786,9 +834,10 @@ int finalize_bn(vk_unet* h, BnL& b, int training, hipStream_t st) {
 int run_conv(vk_unet* h, ConvL& c, const vk_src& s0, const vk_src& s1, int training, hipStream_t st) {
   vk_conv_desc d = conv_desc(h, c, s0, s1);
   BnL& b = h->bns[c.bn];
+  double* const stats = training && !frozen(h, b) ? b.stats : nullptr;
   if (c.halo_fwd && !training && h->splitk_bytes) RET_IF(vk_conv_fwd_splitk(&d, fwd_weights(h, c), c.z, h->ws + h->off_splitk, h->splitk_bytes, st));
-  else if (c.halo_fwd) RET_IF(vk_conv_fwd_packed(&d, fwd_weights(h, c), c.z, nullptr, 0, 0, training ? b.stats : nullptr, st));
-  else RET_IF(vk_conv_fwd(&d, fwd_weights(h, c), c.z, nullptr, 0, 0, training ? b.stats : nullptr, st));
+  else if (c.halo_fwd) RET_IF(vk_conv_fwd_packed(&d, fwd_weights(h, c), c.z, nullptr, 0, 0, stats, st));
+  else RET_IF(vk_conv_fwd(&d, fwd_weights(h, c), c.z, nullptr, 0, 0, stats, st));
   return finalize_bn(h, b, training, st);
 }
 
@@ -1013,14 +1062,26 @@ extern "C" int vk_unet_set_trainable(vk_unet* h, const uint8_t* flags, int n) {
     h->trainable[(size_t)t] = v;
   }
   if (!changed) return VK_OK;
-  h->last_rank = -1;
-  for (const ConvL& c : h->convs) {
-    if (trains(h, c.w_t) || (c.b_t >= 0 && trains(h, c.b_t))) h->last_rank = std::max(h->last_rank, c.rank);
-  }
-  for (const BnL& b : h->bns) {
-    if (trains(h, b.g_t) || trains(h, b.b_t)) h->last_rank = std::max(h->last_rank, b.rank);
-  }
+  update_last_rank(h);
   ++h->mask_version;
+  return VK_OK;
+}
+
+extern "C" int vk_unet_set_bn_frozen(vk_unet* h, const uint8_t* flags, int n) {
+  VK_CHECK_ARG(h && flags, "vk_unet_set_bn_frozen: null argument");
+  VK_CHECK_ARG(n == (int)h->bns.size(), "vk_unet_set_bn_frozen: %d flags for %d BatchNorm layers", n, (int)h->bns.size());
+  static_assert(sizeof(h->bn_frozen) * 8 >= 46, "one bit per BatchNorm layer");
+  uint64_t m = 0;
+  for (int l = 0; l < n; ++l) m |= (flags[l] ? 1ull : 0ull) << l;
+  h->bn_frozen = m;
+  return VK_OK;
+}
+
+extern "C" int vk_unet_set_input_grad(vk_unet* h, float* dx) {
+  VK_CHECK_ARG(h, "vk_unet_set_input_grad: null plan");
+  VK_CHECK_ARG(!dx || h->cfg.training, "vk_unet_set_input_grad: needs a training plan");
+  h->dx_in = dx;
+  update_last_rank(h);
   return VK_OK;
 }
 
@@ -1047,7 +1108,13 @@ extern "C" int vk_unet_forward(vk_unet* h, const float* x, float* logits, int tr
   const int N = h->cfg.N, S = h->cfg.size, SW = h->cfg.width;
   const vk_dtype dt = h->cfg.dtype;
   if (training) {
+    h->bn_frozen_fwd = h->bn_frozen;
     VK_CHECK_HIP(hipMemsetAsync(h->ws + h->off_stats, 0, h->stats_bytes, st));
+    if (h->bn_frozen_fwd) {
+      hipLaunchKernelGGL(k_bn_frozen_affine, dim3((unsigned)h->bns.size()), dim3(128), 0, st, (const BnEvalEntry*)(h->ws + h->off_tab_bn),
+                         h->bn_frozen_fwd, h->params, h->bufs, (float*)(h->ws + h->off_farena), 1e-5f);
+      VK_CHECK_HIP(hipGetLastError());
+    }
   } else {
     hipLaunchKernelGGL(k_bn_eval_all, dim3((unsigned)h->bns.size()), dim3(128), 0, st, (const BnEvalEntry*)(h->ws + h->off_tab_bn),
                        h->params, h->bufs, (float*)(h->ws + h->off_farena), 1e-5f);
@@ -1058,7 +1125,7 @@ extern "C" int vk_unet_forward(vk_unet* h, const float* x, float* logits, int tr
   RET_IF(vk_input_transform(dt, N, S, SW, x, x4, st));
   ConvL& stem = h->convs[h->stem_conv];
   BnL& sbn = h->bns[stem.bn];
-  RET_IF(vk_stem_fwd(dt, N, S, SW, x4, h->ws + h->off_wstem, stem.z, training ? sbn.stats : nullptr, st));
+  RET_IF(vk_stem_fwd(dt, N, S, SW, x4, h->ws + h->off_wstem, stem.z, training && !frozen(h, sbn) ? sbn.stats : nullptr, st));
   RET_IF(finalize_bn(h, sbn, training, st));
   void* pool = h->ws + h->off_pool;
   RET_IF(vk_bn_relu_maxpool(dt, N, S / 2, SW / 2, 64, stem.z, sbn.scale, sbn.shift, pool, (uint8_t*)(h->ws + h->off_argmax), st));
@@ -1115,7 +1182,8 @@ extern "C" int vk_unet_forward(vk_unet* h, const float* x, float* logits, int tr
   vk_src hs = to_src(xd);
   RET_IF(vk_head_fwd(dt, N, S, SW, &hs, h->params + h->head_w_off, h->params + h->head_b_off, logits, st));
   if (training) {
-    hipLaunchKernelGGL(k_inc_i64, dim3(1), dim3(64), 0, st, (int)h->bns.size(), h->nbt);
+    if (h->bn_frozen_fwd) hipLaunchKernelGGL(k_inc_i64_masked, dim3(1), dim3(64), 0, st, (int)h->bns.size(), h->nbt, h->bn_frozen_fwd);
+    else hipLaunchKernelGGL(k_inc_i64, dim3(1), dim3(64), 0, st, (int)h->bns.size(), h->nbt);
     VK_CHECK_HIP(hipGetLastError());
   }
   return VK_OK;
@@ -1142,6 +1210,12 @@ namespace {
 int bn_bwd_phase2(vk_unet* h, BnL& b, int C, size_t pixels, const void* dy, const void* z, int mask_mode, const void* mask_src, void* dz,
                   void* g_out, int g_acc, hipStream_t st) {
   static const int maxc = getenv("VK_BN_APPLY_FUSED_MAXC") ? atoi(getenv("VK_BN_APPLY_FUSED_MAXC")) : VK_BN_APPLY_FUSED_MAXC_DEFAULT;
+  if (frozen(h, b)) {
+    // frozen statistics: (a, 0, 0) is in b.coef since the forward; the sums only give gamma / beta gradients
+    if (trains(h, b.g_t) || trains(h, b.b_t))
+      RET_IF(vk_bn_bwd_coeffs_frozen(C, b.bsums, h->params + b.g_off, b.mean, b.invstd, dgamma_of(h, b), dbeta_of(h, b), b.coef, st));
+    return vk_bn_bwd_apply(h->cfg.dtype, pixels, C, dy, z, mask_mode, b.scale, b.shift, mask_src, b.coef, dz, g_out, g_acc, st);
+  }
   if (C <= maxc)
     return vk_bn_bwd_apply_fused(h->cfg.dtype, pixels, C, dy, z, mask_mode, b.scale, b.shift, mask_src, b.bsums, b.count, h->params + b.g_off,
                                  b.mean, b.invstd, dgamma_of(h, b), dbeta_of(h, b), dz, g_out, g_acc, st);
@@ -1154,7 +1228,7 @@ int bn_bwd_phase2(vk_unet* h, BnL& b, int C, size_t pixels, const void* dy, cons
 int bn_relu_bwd_inplace(vk_unet* h, ConvL& c, bool prereduced, hipStream_t st) {
   BnL& b = h->bns[c.bn];
   const size_t pixels = (size_t)h->cfg.N * c.Hout * c.Wout;
-  if (!prereduced) RET_IF(vk_bn_bwd_reduce(h->cfg.dtype, pixels, c.K, c.g, c.z, 1, b.scale, b.shift, nullptr, b.bsums, st));
+  if (!prereduced && bn_sums_needed(h, b)) RET_IF(vk_bn_bwd_reduce(h->cfg.dtype, pixels, c.K, c.g, c.z, 1, b.scale, b.shift, nullptr, b.bsums, st));
   return bn_bwd_phase2(h, b, c.K, pixels, c.g, c.z, prereduced ? 0 : 1, nullptr, c.g, nullptr, 0, st);
 }
 
@@ -1331,8 +1405,9 @@ int backward_block(vk_unet* h, int bi, hipStream_t st) {
   // see below): no reduce pass here and the apply passes read g as it stands (mask mode 0: one tensor read less each)
   const bool pre = h->tail_prereduced[(size_t)bi] != 0;
   h->tail_prereduced[(size_t)bi] = 0;
+  if (bi > 0) h->tail_prereduced[(size_t)bi - 1] = 0;    // set again below only if this backward's fusion completes block bi - 1's tail
   const int mm = pre ? 0 : 2;
-  if (!pre) RET_IF(vk_bn_bwd_reduce(dt, pixels, k.C, k.gout, c2.z, 2, nullptr, nullptr, k.out, b2.bsums, st));
+  if (!pre && bn_sums_needed(h, b2)) RET_IF(vk_bn_bwd_reduce(dt, pixels, k.C, k.gout, c2.z, 2, nullptr, nullptr, k.out, b2.bsums, st));
   if (k.convd < 0) {
     // identity shortcut: gin (+)= g
     RET_IF(bn_bwd_phase2(h, b2, k.C, pixels, k.gout, c2.z, mm, k.out, c2.g, gin, k.in_has_grad_first ? 1 : 0, st));
@@ -1340,7 +1415,7 @@ int backward_block(vk_unet* h, int bi, hipStream_t st) {
     ConvL& cd = h->convs[k.convd];
     BnL& bd = h->bns[cd.bn];
     RET_IF(bn_bwd_phase2(h, b2, k.C, pixels, k.gout, c2.z, mm, k.out, c2.g, nullptr, 0, st));
-    RET_IF(vk_bn_bwd_reduce(dt, pixels, k.C, k.gout, cd.z, mm, nullptr, nullptr, k.out, bd.bsums, st));
+    if (bn_sums_needed(h, bd)) RET_IF(vk_bn_bwd_reduce(dt, pixels, k.C, k.gout, cd.z, mm, nullptr, nullptr, k.out, bd.bsums, st));
     RET_IF(bn_bwd_phase2(h, bd, k.C, pixels, k.gout, cd.z, mm, k.out, cd.g, nullptr, 0, st));
   }
   // conv2 (data gradient first, weight gradient after it: see backward_decoder)
@@ -1379,41 +1454,59 @@ int backward_block(vk_unet* h, int bi, hipStream_t st) {
   return trains(h, c1.w_t) ? conv_wgrad(h, c1, to_src(xin), null_src(), st) : VK_OK;
 }
 
+// the stem BatchNorm's coefficients (and gamma / beta gradients) from the sums vk_maxpool_bwd_bn_reduce left; a frozen layer has
+// (a, 0, 0) since the forward and runs the launch only for trainable gamma / beta
+int stem_coeffs(vk_unet* h, BnL& b, hipStream_t st) {
+  if (!frozen(h, b))
+    return vk_bn_bwd_coeffs(64, b.bsums, b.count, h->params + b.g_off, b.mean, b.invstd, dgamma_of(h, b), dbeta_of(h, b), b.coef, st);
+  if (!trains(h, b.g_t) && !trains(h, b.b_t)) return VK_OK;
+  return vk_bn_bwd_coeffs_frozen(64, b.bsums, h->params + b.g_off, b.mean, b.invstd, dgamma_of(h, b), dbeta_of(h, b), b.coef, st);
+}
+
 int backward_stem(vk_unet* h, hipStream_t st) {
   const int N = h->cfg.N, S = h->cfg.size, SW = h->cfg.width;
   ConvL& stem = h->convs[h->stem_conv];
   if (!need_from(h, h->bns[stem.bn].rank)) return VK_OK;
+  BnL& b = h->bns[stem.bn];
+  const bool want_w = trains(h, stem.w_t);
+  const float* const w = h->params + stem.w_off;
   // stem.g holds the skip gradient of f1 (from decoder block 3); add the maxpool path
   if (getenv("VK_NO_POOL_BNR_FUSION")) {
     RET_IF(vk_maxpool_bwd(h->cfg.dtype, N, S / 2, SW / 2, 64, h->ws + h->off_gpool, (const uint8_t*)(h->ws + h->off_argmax), stem.g, st));
     RET_IF(bn_relu_bwd_inplace(h, stem, false, st));
   } else {
-    // one pass: maxpool backward + mask + BN-backward sums (saves a read-modify-write and a read of the 256x256x64 gradient)
-    BnL& b = h->bns[stem.bn];
+    // one pass: maxpool backward + mask + BN-backward sums (saves a read-modify-write and a read of the 256x256x64 gradient; with
+    // frozen statistics and gamma / beta the sums have no reader — the kernel writes them anyway, ~1 % of its traffic)
     RET_IF(vk_maxpool_bwd_bn_reduce(h->cfg.dtype, N, S / 2, SW / 2, 64, h->ws + h->off_gpool, (const uint8_t*)(h->ws + h->off_argmax), stem.z,
                                     b.scale, b.shift, stem.g, b.bsums, st));
-    // r04: the stem's dz has ONE reader, the weight gradient below (no data gradient: the input needs none) — the 16-bit kernel forms
-    // dz = a*g + b*z + c itself while staging, so the apply pass (g, z -> dz: 805 MB at bs 32) is not run.  VK_NO_STEM_BNA=1: the pass
-    // A frozen stem convolution needs no dz at all: the coefficient launch alone gives the BatchNorm's gamma / beta gradients.
-    if (!trains(h, stem.w_t))
-      return vk_bn_bwd_coeffs(64, b.bsums, b.count, h->params + b.g_off, b.mean, b.invstd, dgamma_of(h, b), dbeta_of(h, b), b.coef, st);
+    // r04: dz's readers — the weight gradient and (input gradient, vk_unet_set_input_grad) the data gradient — form dz = a*g + b*z + c
+    // themselves while staging (16-bit), so the apply pass (g, z -> dz: 805 MB at bs 32) is not run: folding it into BOTH readers reads
+    // g and z twice (1.07 GB at bs 32) where the pass + two dz readers would move 1.34 GB and add a launch.  VK_NO_STEM_BNA=1: the pass
+    // A frozen stem convolution without an input gradient needs no dz at all: the coefficient launch alone gives gamma / beta gradients.
+    if (!want_w && !h->dx_in) return stem_coeffs(h, b, st);
     if (h->cfg.dtype != VK_F32 && !getenv("VK_NO_STEM_BNA")) {
-      RET_IF(vk_bn_bwd_coeffs(64, b.bsums, b.count, h->params + b.g_off, b.mean, b.invstd, dgamma_of(h, b), dbeta_of(h, b), b.coef, st));
-      hipStream_t ws;
-      RET_IF(wgrad_stream(h, st, &ws));
-      const int rc = vk_stem_wgrad_bn(h->cfg.dtype, N, S, SW, h->ws + h->off_x4, stem.g, stem.z, b.coef, h->grads + stem.w_off,
-                                      h->ws + h->off_wslab, VK_WGRAD_WORKSPACE_BYTES, ws);
-      if (rc != VK_ERR_UNSUPPORTED) return rc;
+      RET_IF(stem_coeffs(h, b, st));
+      int rc = VK_OK;
+      if (want_w) {
+        hipStream_t ws;
+        RET_IF(wgrad_stream(h, st, &ws));
+        rc = vk_stem_wgrad_bn(h->cfg.dtype, N, S, SW, h->ws + h->off_x4, stem.g, stem.z, b.coef, h->grads + stem.w_off,
+                              h->ws + h->off_wslab, VK_WGRAD_WORKSPACE_BYTES, ws);
+        if (rc != VK_OK && rc != VK_ERR_UNSUPPORTED) return rc;
+      }
+      if (rc == VK_OK) return h->dx_in ? vk_stem_dgrad(h->cfg.dtype, N, S, SW, stem.g, stem.z, b.coef, w, h->dx_in, st) : VK_OK;
       // (shape outside the tile kernel: coefficients are in place, finish with the separate apply pass)
       RET_IF(vk_bn_bwd_apply(h->cfg.dtype, (size_t)N * (S / 2) * (SW / 2), 64, stem.g, stem.z, 0, b.scale, b.shift, nullptr, b.coef, stem.g, nullptr, 0, st));
     } else {
       RET_IF(bn_relu_bwd_inplace(h, stem, true, st));
     }
   }
-  if (!trains(h, stem.w_t)) return VK_OK;
-  hipStream_t ws;
-  RET_IF(wgrad_stream(h, st, &ws));
-  return vk_stem_wgrad(h->cfg.dtype, N, S, SW, h->ws + h->off_x4, stem.g, h->grads + stem.w_off, h->ws + h->off_wslab, VK_WGRAD_WORKSPACE_BYTES, ws);
+  if (want_w) {
+    hipStream_t ws;
+    RET_IF(wgrad_stream(h, st, &ws));
+    RET_IF(vk_stem_wgrad(h->cfg.dtype, N, S, SW, h->ws + h->off_x4, stem.g, h->grads + stem.w_off, h->ws + h->off_wslab, VK_WGRAD_WORKSPACE_BYTES, ws));
+  }
+  return h->dx_in ? vk_stem_dgrad(h->cfg.dtype, N, S, SW, stem.g, nullptr, nullptr, w, h->dx_in, st) : VK_OK;
 }
 
 // the collected weight gradients of a stage: one batched launch (tables built once per stage and per workgroup budget), a single one

@@ -51,6 +51,9 @@ class _Plan:
         self.loss_out = torch.zeros(4, dtype=torch.float32, device=dev)
         self.weights_version = None
         self.mask = None                    # trainable flags the engine holds (vk_unet_set_trainable); None: not pushed yet
+        self.bn_frozen = None               # BatchNorm modes the engine holds (vk_unet_set_bn_frozen); None: not pushed (all train)
+        self.dx: Optional[torch.Tensor] = None     # fp32 [N,3,H,W] input gradient the engine writes (vk_unet_set_input_grad)
+        self.dx_on = False
         self.bucket_trainable: List[bool] = []
         self.nbuckets = L.vk_unet_num_buckets(h)
         self.buckets: List[Tuple[int, int]] = []
@@ -76,6 +79,23 @@ class _Plan:
         self.mask = mask
         ranges = [(off, off + numel) for (off, numel), t in zip(model._param_ranges, mask) if t]
         self.bucket_trainable = [any(a < b1 and b0 < b for a, b in ranges) for b0, b1 in self.buckets]
+
+    def set_bn_frozen(self, flags: Tuple[bool, ...]):
+        """Hand the engine one frozen-statistics flag per BatchNorm layer (host only; done when the flags change)."""
+        if flags == self.bn_frozen or (self.bn_frozen is None and not any(flags)):
+            return
+        arr = (C.c_uint8 * len(flags))(*flags)
+        check(lib().vk_unet_set_bn_frozen(self.h, arr, len(flags)), "vk_unet_set_bn_frozen")
+        self.bn_frozen = flags
+
+    def set_input_grad(self, on: bool, device):
+        """Point the engine's input-gradient output at the plan's buffer, or at nothing (host only; done when it changes)."""
+        if on == self.dx_on:
+            return
+        if on and self.dx is None:
+            self.dx = torch.empty(self.N, 3, self.H, self.W, dtype=torch.float32, device=device)
+        check(lib().vk_unet_set_input_grad(self.h, self.dx.data_ptr() if on else None), "vk_unet_set_input_grad")
+        self.dx_on = on
 
     def debug_tensor(self, name: str) -> torch.Tensor:
         """Copy of a named intermediate (NHWC) — parity/debug only."""
@@ -105,12 +125,16 @@ class _UnetFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, anchor, model, plan, mask):
         ctx.model, ctx.plan, ctx.mask = model, plan, mask      # requires_grad as it was when the forward ran (torch records it then)
+        ctx.x_dtype, ctx.x_device = x.dtype, x.device
         return model._run_forward(plan, x, True)
 
     @staticmethod
     def backward(ctx, g):
-        ctx.model._run_backward(ctx.plan, g.contiguous().float(), ctx.mask)
-        return None, None, None, None, None
+        want_dx = bool(ctx.needs_input_grad[0])
+        ctx.model._run_backward(ctx.plan, g.contiguous().float(), ctx.mask, want_dx)
+        # the plan's buffer is rewritten by the next backward: hand autograd a copy in x's dtype
+        dx = ctx.plan.dx.to(dtype=ctx.x_dtype, copy=True) if want_dx else None
+        return dx, None, None, None, None
 
 
 class Unet(nn.Module):
@@ -202,6 +226,7 @@ class Unet(nn.Module):
         self._anchor = torch.zeros((), requires_grad=True, device=self._flat["params"].device)
         self._param_list = [self._leaves[t[0]][0]._parameters[self._leaves[t[0]][1]] for t in self._table if t[1] in (0, 1)]
         self._param_ranges = [(t[3], t[4]) for t in self._table if t[1] in (0, 1)]
+        self._bn_modules = [self._leaves[t[0]][0] for t in self._table if t[1] == 3]
 
     def _apply(self, fn, recurse=True):
         for k in ("params", "grads", "bufs", "nbt"):
@@ -310,6 +335,11 @@ class Unet(nn.Module):
     def _trainable_mask(self) -> Tuple[bool, ...]:
         return tuple(bool(p.requires_grad) for p in self._param_list)
 
+    def _bn_frozen_flags(self) -> Tuple[bool, ...]:
+        """One flag per BatchNorm layer, in the engine's order (the num_batches_tracked entries of the tensor table): the layer's mode
+        is the ``training`` flag of the module that owns its weight / running stats (``encoder.bn1``, ...), as in torch."""
+        return tuple(not m.training for m in self._bn_modules)
+
     def mark_weights_dirty(self):
         """Call after writing the flat parameter buffer through a raw pointer (FusedAdamW does)."""
         self._dirty += 1
@@ -349,15 +379,18 @@ class Unet(nn.Module):
             check(L.vk_unet_refresh_weights(plan.h, st), "vk_unet_refresh_weights")
             plan.weights_version = ver
         x = x.detach().contiguous().float()
+        if training:
+            plan.set_bn_frozen(self._bn_frozen_flags())      # per-layer BatchNorm modes; the engine keeps them for the backward
         logits = torch.empty(plan.N, 1, plan.H, plan.W, dtype=torch.float32, device=x.device)
         check(L.vk_unet_forward(plan.h, x.data_ptr(), logits.data_ptr(), 1 if training else 0, st), "vk_unet_forward")
         plan._last_x = x      # keep the input alive until backward has consumed the plan's x4 copy
         return logits
 
-    def _run_backward(self, plan: _Plan, dlogits: Optional[torch.Tensor], mask: Tuple[bool, ...]):
+    def _run_backward(self, plan: _Plan, dlogits: Optional[torch.Tensor], mask: Tuple[bool, ...], want_dx: bool = False):
         L = lib()
         st = _lib.current_stream()
         plan.set_trainable(self, mask)
+        plan.set_input_grad(want_dx, self._flat["params"].device)
         if all(mask):
             fresh = next(iter(self.parameters())).grad is None
         else:
@@ -433,16 +466,20 @@ class Unet(nn.Module):
         else:
             dtype = self.compute_dtype
         mask = self._trainable_mask()
-        need_grad = self.training and torch.is_grad_enabled() and any(mask)    # nothing trainable: a plain train-mode forward, as torch
-        plan = self.plan_for(N, S, dtype, need_grad or self.training)
+        # a graph iff grad mode is on and something needs a gradient (a parameter or the input), in either mode of the root; the
+        # BatchNorm layers run in their own modules' modes (_bn_frozen_flags) on a training plan.  Without a graph and with every layer
+        # in eval mode: the eval plan, as before.
+        need_grad = torch.is_grad_enabled() and (any(mask) or x.requires_grad)
+        all_frozen = all(self._bn_frozen_flags())
+        plan = self.plan_for(N, S, dtype, need_grad or not all_frozen)
         if need_grad:
             return _UnetFn.apply(x, self._anchor, self, plan, mask)
-        return self._run_forward(plan, x, self.training)
+        return self._run_forward(plan, x, not all_frozen)
 
     # ------------------------------------------------------------------ fused step (no autograd graph)
     def loss_and_backward(self, x: torch.Tensor, y: torch.Tensor, grad_scale: float = 1.0,
                           dtype: Optional[torch.dtype] = None) -> torch.Tensor:
-        """forward (batch-stat BN) + BCE+Dice + backward in one call; the engine's loss kernel feeds the
+        """forward (BatchNorm layers in their modules' modes) + BCE+Dice + backward in one call; the engine's loss kernel feeds the
         head gradient directly.  Returns a device tensor [total, bce, dice] (no host sync).
         Equivalent to train.py:436-448 ``logits = model(x); loss = bce + dice; loss.backward()``; ``requires_grad`` of the parameters
         is read at this call (frozen ones get no gradient, see INTEGRATION.md "Fine-tuning")."""

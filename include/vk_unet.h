@@ -411,6 +411,33 @@ int vk_head_bwd_fused(vk_dtype dtype, int N, int H, int W, const vk_src* src, co
 int vk_bce_dice_loss(size_t count, const float* logits, const float* target, double* sums, float* loss_out,
                      float* dlogits, float grad_scale, float w_bce, float w_dice, void* stream);
 
+/* ---- more than one class (1 <= C <= 16): the 16 -> C head and its two losses (multiclass.hip).  The binary model keeps the kernels
+ * above; these run for a plan created with vk_unet_create_ex(classes > 1) and for the loss modules of any C.
+ * Head filter: KRSC [C][3][3][16] fp32, bias [C]; logits / dlogits fp32 NCHW [N][C][H][W] (class planes); src as in vk_head_fwd. */
+int vk_head_fwd_multi(vk_dtype dtype, int N, int H, int W, int C, const vk_src* src, const float* w, const float* bias, float* logits,
+                      void* stream);
+/* dy[N][H][W][16] (element type) = data gradient of the head input, dw [C][3][3][16] += weight gradient, dbias [C] += bias gradient.
+ * bnr (optional): the BatchNorm+ReLU backward reduce of the head's input layer fused into the dy pass, as in vk_head_bwd_fused.
+ * workspace (required, vk_head_multi_workspace_bytes(C) is always enough): per-workgroup partials of dw / dbias that a second launch
+ * adds in workgroup order, so dw / dbias are bit-reproducible. */
+size_t vk_head_multi_workspace_bytes(int C);
+int vk_head_bwd_multi(vk_dtype dtype, int N, int H, int W, int C, const vk_src* src, const float* w, const float* dlogits, void* dy,
+                      float* dw, float* dbias, const vk_bnr* bnr, void* workspace, size_t workspace_bytes, void* stream);
+/* Device scratch of the two losses below for logits [N][C][HW] (8-byte aligned). */
+size_t vk_multi_loss_workspace_bytes(int N, int C, int HW);
+/* loss = w_bce * BCEWithLogitsLoss()(x, y) + w_dice * smp DiceLoss("multilabel")(x, y); x, y fp32 [N][C][HW].
+ * Per class c: I = sum sigmoid(x) y, P = sum sigmoid(x), T = sum y over (N, HW) in fp64 (per-workgroup partials added in a fixed
+ * order); dice_c = (1 - 2 I / max(P + T, 1e-7)) [T > 0]; dice = mean over c; bce = mean over N C HW.
+ * loss_out float[4] = {total, bce, dice, 0}; dlogits (optional) = grad_scale * d total / dx. */
+int vk_multilabel_loss(int N, int C, int HW, const float* logits, const float* target, void* workspace, size_t workspace_bytes,
+                       float* loss_out, float* dlogits, float grad_scale, float w_bce, float w_dice, void* stream);
+/* loss = w_ce * CrossEntropyLoss()(x, t) + w_dice * smp DiceLoss("multiclass")(x, t); x fp32 [N][C][HW], t int64 [N][HW] in [0, C).
+ * Dice as above on softmax(x) against one_hot(t); ce = mean over N HW.  A label outside [0, C) is an argument error reported on the
+ * device: loss_out = {NaN, NaN, NaN, number of bad labels} (loss_out[3] = 0 when every label is valid); such pixels add nothing and
+ * get a zero gradient. */
+int vk_multiclass_loss(int N, int C, int HW, const float* logits, const int64_t* target, void* workspace, size_t workspace_bytes,
+                       float* loss_out, float* dlogits, float grad_scale, float w_ce, float w_dice, void* stream);
+
 /* Thresholded Dice / IoU of the reference's validate() (train.py:230-255 `dice_coef`, :259-281 `iou_coef`, :518-522):
  * per image i of `per_image` elements, pred = (p > threshold) as 0/1, I = sum pred*t, P = sum pred, T = sum t;
  * dice_i = (2 I + eps) / (P + T + eps), iou_i = (I + eps) / (P + T - I + eps) in fp32.
@@ -486,6 +513,10 @@ typedef struct {
 } vk_tensor_info;
 
 int vk_unet_create(const vk_unet_config* cfg, vk_unet** out);
+/* smp.Unet(..., classes=C) for 1 <= C <= 16: segmentation_head.0 is [C][16][3][3] + bias [C], the logits [N][C][S][S].
+ * vk_unet_create is classes = 1 (the binary model: same kernels, launches and workspace as before). */
+int vk_unet_create_ex(const vk_unet_config* cfg, int classes, vk_unet** out);
+int vk_unet_num_classes(const vk_unet* h);
 void vk_unet_destroy(vk_unet* h);
 /* Optional: run a training plan's weight-gradient kernels on a second, library-owned HIP stream beside the caller's stream
  * (fork per layer once dz is final, join at the end of every backward stage, before the stage's gradient bucket may be
@@ -509,12 +540,20 @@ int vk_unet_bind(vk_unet* h, float* params, float* grads, float* bn_buffers, int
 /* re-pack the compute copies of the weights after the fp32 master changed (load_state_dict, optimizer step) */
 int vk_unet_refresh_weights(vk_unet* h, void* stream);
 
-/* x: fp32 NCHW [N][3][S][S]; logits: fp32 [N][1][S][S].  training=1: batch statistics + running-stat update */
+/* x: fp32 NCHW [N][3][S][S]; logits: fp32 [N][C][S][S] (C = classes).  training=1: batch statistics + running-stat update */
 int vk_unet_forward(vk_unet* h, const float* x, float* logits, int training, void* stream);
 /* target fp32 [N][1][S][S]; loss_out float[3]; computes dlogits for backward when the plan is a training plan */
 int vk_unet_loss(vk_unet* h, const float* logits, const float* target, float* loss_out, float grad_scale,
                  float w_bce, float w_dice, void* stream);
-/* dlogits: fp32 [N][1][S][S] gradient of the loss wrt the logits, or NULL to use the one vk_unet_loss
+/* Loss of any plan: mode VK_LOSS_BINARY (classes == 1; = vk_unet_loss), VK_LOSS_MULTILABEL (target fp32 [N][C][S][S]; with one class
+ * it is the binary loss) or VK_LOSS_MULTICLASS (classes >= 2; target int64 [N][S][S], see vk_multiclass_loss for bad labels).  A mode
+ * that does not fit the plan's classes is refused.  w_ce weighs the BCE / cross-entropy term. */
+#define VK_LOSS_BINARY 0
+#define VK_LOSS_MULTILABEL 1
+#define VK_LOSS_MULTICLASS 2
+int vk_unet_loss_ex(vk_unet* h, int mode, const void* logits, const void* target, float* loss_out, float grad_scale, float w_ce,
+                    float w_dice, void* stream);
+/* dlogits: fp32 [N][C][S][S] gradient of the loss wrt the logits, or NULL to use the one vk_unet_loss
  * left in the workspace.  Runs backward stages [stage_begin, stage_end); stage i completes gradient bucket i.  Gradients are
  * accumulated into the flat grad buffer (caller zeroes it once per step, e.g. via vk_unet_zero_grad).
  * Only the gradients of TRAINABLE tensors (vk_unet_set_trainable) are written; the element ranges of frozen tensors are left

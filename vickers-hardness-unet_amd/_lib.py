@@ -14,6 +14,7 @@ LIB_PATH = Path(os.environ["VK_LIB"]) if os.environ.get("VK_LIB") else PKG_DIR /
 CSRC = PKG_DIR / "csrc"
 
 VK_F32, VK_BF16, VK_F16 = 0, 1, 2
+VK_LOSS_BINARY, VK_LOSS_MULTILABEL, VK_LOSS_MULTICLASS = 0, 1, 2
 
 
 class VkError(RuntimeError):
@@ -128,6 +129,12 @@ SIGNATURES = {
     "vk_dec4_tail_eval": (ci, [ci, ci, ci, ci, P(vk_src), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "vk_head_bwd": (ci, [ci, ci, ci, ci, P(vk_src), vp, vp, vp, vp, vp, vp, sz, vp]),
     "vk_bce_dice_loss": (ci, [sz, vp, vp, vp, vp, vp, cf, cf, cf, vp]),
+    "vk_head_fwd_multi": (ci, [ci, ci, ci, ci, ci, P(vk_src), vp, vp, vp, vp]),
+    "vk_head_multi_workspace_bytes": (sz, [ci]),
+    "vk_head_bwd_multi": (ci, [ci, ci, ci, ci, ci, P(vk_src), vp, vp, vp, vp, vp, P(vk_bnr), vp, sz, vp]),
+    "vk_multi_loss_workspace_bytes": (sz, [ci, ci, ci]),
+    "vk_multilabel_loss": (ci, [ci, ci, ci, vp, vp, vp, sz, vp, vp, cf, cf, cf, vp]),
+    "vk_multiclass_loss": (ci, [ci, ci, ci, vp, vp, vp, sz, vp, vp, cf, cf, cf, vp]),
     "vk_seg_metrics_workspace_bytes": (C.c_size_t, [ci]),
     "vk_seg_metrics": (ci, [ci, sz, vp, vp, ci, cf, cf, vp, sz, vp, vp]),
     "vk_adamw_step": (ci, [sz, vp, vp, vp, vp, cf, cf, cf, cf, cf, ci, cf, vp, vp, ci, vp]),
@@ -137,6 +144,8 @@ SIGNATURES = {
     "vk_adamw_segment_blocks": (ci, [ci, P(i64), P(C.c_int32), ci]),
     "vk_adamw_step_amp_segments": (ci, [ci, vp, ci, vp, vp, vp, vp, vp, cf, cf, cf, cf, cf, vp, cf, vp, vp, vp, vp]),
     "vk_unet_create": (ci, [P(vk_unet_config), P(vp)]),
+    "vk_unet_create_ex": (ci, [P(vk_unet_config), ci, P(vp)]),
+    "vk_unet_num_classes": (ci, [vp]),
     "vk_unet_destroy": (None, [vp]),
     "vk_unet_set_side_stream": (ci, [vp, ci]),
     "vk_unet_num_tensors": (ci, [vp]),
@@ -150,6 +159,7 @@ SIGNATURES = {
     "vk_unet_refresh_weights": (ci, [vp, vp]),
     "vk_unet_forward": (ci, [vp, vp, vp, ci, vp]),
     "vk_unet_loss": (ci, [vp, vp, vp, vp, cf, cf, cf, vp]),
+    "vk_unet_loss_ex": (ci, [vp, ci, vp, vp, vp, cf, cf, cf, vp]),
     "vk_unet_backward": (ci, [vp, vp, ci, ci, vp]),
     "vk_unet_set_trainable": (ci, [vp, P(C.c_uint8), ci]),
     "vk_unet_set_bn_frozen": (ci, [vp, P(C.c_uint8), ci]),

@@ -399,10 +399,11 @@ using namespace vk;
 constexpr int kMaxStages = 16;
 constexpr int kMaxBatch = 40;                       // layers in one batched weight-gradient launch (the model has 35 of the class)
 constexpr size_t kEngineSlabBytes = 176u << 20;     // slab workspace of a training plan: partial tiles of a whole-backward batch (~950 x 147 KB)
-constexpr size_t kGradScratchFloats = 2048;         // frozen-gradient sink: dgamma [512] | dbeta [512] | head dw [144] | head db
+constexpr size_t kGradScratchFloats = 2048;         // frozen-gradient sink: dgamma [512] | dbeta [512] | head dw [144 C] | head db [C]
 
 struct vk_unet {
   vk_unet_config cfg;
+  int classes = 1;               // output channels of the head (vk_unet_create_ex); 1 is the binary model and its kernels
   int eb;                        // element bytes of the activation dtype
   std::vector<vk_tensor_info> infos;
   int n_ptensors = 0;            // parameter tensors (kinds 0 and 1) in `infos`
@@ -469,6 +470,7 @@ struct vk_unet {
   std::vector<CastRange> cast_tab;
   size_t off_tab_cast = 0;
   size_t off_gscratch = 0;          // sink of the gamma / beta / head gradients of frozen tensors (never read)
+  size_t off_mloss = 0, mloss_bytes = 0;   // classes > 1: partial sums of vk_multilabel_loss / vk_multiclass_loss
   std::vector<BnEvalEntry> bn_tab;
   std::map<std::string, std::pair<void*, std::vector<int>>> debug;
 
@@ -521,7 +523,7 @@ int add_conv(vk_unet* h, const std::string& name, int Cin, int K, int R, int str
   h->n_params += (int64_t)align_up((size_t)numel, 4);
   if (bias) {
     c.b_t = add_info(h, name + ".bias", 1, {K}, h->n_params, K);
-    h->n_params += 4;
+    h->n_params += (int64_t)align_up((size_t)K, 4);
   }
   h->convs.push_back(c);
   return (int)h->convs.size() - 1;
@@ -610,9 +612,9 @@ void build_topology(vk_unet* h) {
   // --- head
   const int64_t head_start = h->n_params;
   (void)head_start;
-  h->head_conv = add_conv(h, "segmentation_head.0", 16, 1, 3, 1, 1, S, SW, /*bias=*/true);
+  h->head_conv = add_conv(h, "segmentation_head.0", 16, h->classes, 3, 1, 1, S, SW, /*bias=*/true);
   h->head_w_off = h->convs[h->head_conv].w_off;
-  h->head_b_off = h->head_w_off + 144;
+  h->head_b_off = h->head_w_off + (int64_t)align_up((size_t)144 * h->classes, 4);
   h->n_params = (int64_t)align_up((size_t)h->n_params, 64);
   // --- dgrad arena offsets
   for (size_t i = 0; i < h->convs.size(); ++i) {
@@ -673,6 +675,9 @@ void update_last_rank(vk_unet* h) {
   if (h->dx_in) h->last_rank = h->input_rank;
 }
 
+// the frozen-gradient sink: dgamma [512] | dbeta [512] | head dw [144 C] | head db [C]; the binary model keeps its 2048 floats
+size_t grad_scratch_floats(const vk_unet* h) { return h->classes == 1 ? kGradScratchFloats : align_up(1024 + 145 * (size_t)h->classes, 64); }
+
 void layout_workspace(vk_unet* h) {
   const int N = h->cfg.N, S = h->cfg.size, SW = h->cfg.width, eb = h->eb;
   const bool tr = h->cfg.training != 0;
@@ -709,7 +714,7 @@ void layout_workspace(vk_unet* h) {
     size_t mx = 0;
     for (const DecL& d : h->decs) mx = std::max(mx, (size_t)N * d.H * d.W * d.Cup * eb);
     h->off_dup = take(mx);
-    h->off_dlogits = take((size_t)N * S * SW * 4);
+    h->off_dlogits = take((size_t)N * h->classes * S * SW * 4);
   }
   h->off_loss_sums = take(8 * sizeof(double));
   // per-BN statistics (one zero region) and float arena
@@ -737,7 +742,11 @@ void layout_workspace(vk_unet* h) {
   h->off_tab_pack = take(h->convs.size() * sizeof(PackEntry));
   h->off_tab_cast = take(h->convs.size() * sizeof(CastRange));
   h->off_tab_bn = take(h->bns.size() * sizeof(BnEvalEntry));
-  h->off_gscratch = tr ? take(kGradScratchFloats * sizeof(float)) : 0;      // last: every other offset is what it was without it
+  h->off_gscratch = tr ? take(grad_scratch_floats(h) * sizeof(float)) : 0;      // last: every other offset is what it was without it
+  if (h->classes > 1) {            // after everything else: a binary plan's layout does not change
+    h->mloss_bytes = vk_multi_loss_workspace_bytes(N, h->classes, S * SW);
+    h->off_mloss = take(h->mloss_bytes);
+  }
   h->ws_bytes = off;
 }
 
@@ -766,7 +775,8 @@ void assign_pointers(vk_unet* h) {
   h->debug["pool"] = {ws + h->off_pool, {N, S / 4, SW / 4, 64}};
   if (h->cfg.training) {
     h->debug["gpool"] = {ws + h->off_gpool, {N, S / 4, SW / 4, 64}};
-    h->debug["dlogits"] = {ws + h->off_dlogits, {N, S, SW, 1}};
+    if (h->classes == 1) h->debug["dlogits"] = {ws + h->off_dlogits, {N, S, SW, 1}};
+    else h->debug["dlogits"] = {ws + h->off_dlogits, {N, h->classes, S, SW}};
   }
   double* sp = (double*)(ws + h->off_stats);
   double* bp = (double*)(ws + h->off_bsums);
@@ -875,14 +885,18 @@ extern "C" int vk_debug_hold_cus(int workgroups, int threads, int lds_bytes, int
   return VK_OK;
 }
 
-extern "C" int vk_unet_create(const vk_unet_config* cfg, vk_unet** out) {
+extern "C" int vk_unet_create(const vk_unet_config* cfg, vk_unet** out) { return vk_unet_create_ex(cfg, 1, out); }
+
+extern "C" int vk_unet_create_ex(const vk_unet_config* cfg, int classes, vk_unet** out) {
   VK_CHECK_ARG(cfg && out, "vk_unet_create: null argument");
+  VK_CHECK_ARG(classes >= 1 && classes <= 16, "vk_unet_create_ex: classes=%d is outside 1..16 (one 16-wide tile of head outputs)", classes);
   const int width = cfg->width > 0 ? cfg->width : cfg->size;
   VK_CHECK_ARG(cfg->N >= 1 && cfg->size >= 32 && cfg->size % 32 == 0 && width >= 32 && width % 32 == 0,
                "Wrong input shape height=%d, width=%d: must be divisible by 32", cfg->size, width);
   VK_CHECK_ARG(cfg->dtype == VK_F32 || cfg->dtype == VK_BF16 || cfg->dtype == VK_F16, "vk_unet_create: bad dtype");
   vk_unet* h = new vk_unet();
   h->cfg = *cfg;
+  h->classes = classes;
   h->cfg.width = width;
   h->eb = cfg->dtype == VK_F32 ? 4 : 2;
   build_topology(h);
@@ -891,6 +905,8 @@ extern "C" int vk_unet_create(const vk_unet_config* cfg, vk_unet** out) {
   *out = h;
   return VK_OK;
 }
+
+extern "C" int vk_unet_num_classes(const vk_unet* h) { return h ? h->classes : 0; }
 
 extern "C" void vk_unet_destroy(vk_unet* h) {
   if (!h) return;
@@ -1166,7 +1182,7 @@ extern "C" int vk_unet_forward(vk_unet* h, const float* x, float* logits, int tr
     // tile's redundant halo work and three barriers cost more than the 33 MB per image they save against the streaming kernels — so
     // large plans keep the three launches.  VK_NO_TAIL_FUSION=1 / VK_TAIL_FUSION=1: never / always
     const bool small_plan = (size_t)N * S * SW <= 4u * 512 * 512;
-    if (!training && i + 1 == h->decs.size() && dt != VK_F32 && !d.Cskip && d.Cup == 32 && c1.K == 16 && c2.K == 16 && c1.halo_fwd &&
+    if (!training && h->classes == 1 && i + 1 == h->decs.size() && dt != VK_F32 && !d.Cskip && d.Cup == 32 && c1.K == 16 && c2.K == 16 && c1.halo_fwd &&
         !c2.halo_fwd && S % 16 == 0 && SW % 16 == 0 && !getenv("VK_NO_TAIL_FUSION") && (small_plan || getenv("VK_TAIL_FUSION"))) {
       const vk_src s0 = to_src(xd, 1);
       const BnL& b1 = h->bns[c1.bn];
@@ -1180,7 +1196,8 @@ extern "C" int vk_unet_forward(vk_unet* h, const float* x, float* logits, int tr
   }
   // head
   vk_src hs = to_src(xd);
-  RET_IF(vk_head_fwd(dt, N, S, SW, &hs, h->params + h->head_w_off, h->params + h->head_b_off, logits, st));
+  if (h->classes == 1) RET_IF(vk_head_fwd(dt, N, S, SW, &hs, h->params + h->head_w_off, h->params + h->head_b_off, logits, st));
+  else RET_IF(vk_head_fwd_multi(dt, N, S, SW, h->classes, &hs, h->params + h->head_w_off, h->params + h->head_b_off, logits, st));
   if (training) {
     if (h->bn_frozen_fwd) hipLaunchKernelGGL(k_inc_i64_masked, dim3(1), dim3(64), 0, st, (int)h->bns.size(), h->nbt, h->bn_frozen_fwd);
     else hipLaunchKernelGGL(k_inc_i64, dim3(1), dim3(64), 0, st, (int)h->bns.size(), h->nbt);
@@ -1189,9 +1206,27 @@ extern "C" int vk_unet_forward(vk_unet* h, const float* x, float* logits, int tr
   return VK_OK;
 }
 
+extern "C" int vk_unet_loss_ex(vk_unet* h, int mode, const void* logits, const void* target, float* loss_out, float grad_scale,
+                               float w_ce, float w_dice, void* stream) {
+  VK_CHECK_ARG(h && h->bound && logits && target && loss_out, "vk_unet_loss_ex: plan not bound or null tensor");
+  VK_CHECK_ARG(mode == VK_LOSS_BINARY || mode == VK_LOSS_MULTILABEL || mode == VK_LOSS_MULTICLASS, "vk_unet_loss_ex: bad mode %d", mode);
+  VK_CHECK_ARG(mode != VK_LOSS_BINARY || h->classes == 1, "vk_unet_loss_ex: the binary loss needs classes == 1 (the plan has %d)", h->classes);
+  VK_CHECK_ARG(mode != VK_LOSS_MULTICLASS || h->classes >= 2, "vk_unet_loss_ex: the multi-class loss needs classes >= 2");
+  // one class: multi-label is the binary loss (sigmoid, BCE mean, one Dice term), and runs its kernels
+  if (h->classes == 1) return vk_unet_loss(h, (const float*)logits, (const float*)target, loss_out, grad_scale, w_ce, w_dice, stream);
+  const int N = h->cfg.N, HW = h->cfg.size * h->cfg.width;
+  float* dl = h->cfg.training ? (float*)(h->ws + h->off_dlogits) : nullptr;
+  if (mode == VK_LOSS_MULTILABEL)
+    return vk_multilabel_loss(N, h->classes, HW, (const float*)logits, (const float*)target, h->ws + h->off_mloss, h->mloss_bytes, loss_out,
+                              dl, grad_scale, w_ce, w_dice, stream);
+  return vk_multiclass_loss(N, h->classes, HW, (const float*)logits, (const int64_t*)target, h->ws + h->off_mloss, h->mloss_bytes, loss_out,
+                            dl, grad_scale, w_ce, w_dice, stream);
+}
+
 extern "C" int vk_unet_loss(vk_unet* h, const float* logits, const float* target, float* loss_out, float grad_scale, float w_bce,
                             float w_dice, void* stream) {
   VK_CHECK_ARG(h && h->bound && logits && target && loss_out, "vk_unet_loss: plan not bound or null tensor");
+  VK_CHECK_ARG(h->classes == 1, "vk_unet_loss: the binary loss needs classes == 1; use vk_unet_loss_ex");
   const size_t count = (size_t)h->cfg.N * h->cfg.size * h->cfg.width;
   float* dl = h->cfg.training ? (float*)(h->ws + h->off_dlogits) : nullptr;
   return vk_bce_dice_loss(count, logits, target, (double*)(h->ws + h->off_loss_sums), loss_out, dl, grad_scale, w_bce, w_dice, stream);
@@ -1555,9 +1590,15 @@ int backward_stage(vk_unet* h, const float* dlogits, int stage, hipStream_t st) 
       ConvL& last = h->convs[h->decs[4].conv2];
       const ConvL& head = h->convs[h->head_conv];
       float* const hdw = grad_or_sink(h, head.w_t, h->head_w_off, 1024);
-      float* const hdb = grad_or_sink(h, head.b_t, h->head_b_off, 1024 + 144);
+      float* const hdb = grad_or_sink(h, head.b_t, h->head_b_off, 1024 + 144 * h->classes);
       vk_src hs = to_src(bn_act(h, last));
-      {
+      if (h->classes > 1) {
+        vk_bnr r = bnr_of(h, last);
+        const float* dl = dlogits ? dlogits : (const float*)(h->ws + h->off_dlogits);
+        RET_IF(vk_head_bwd_multi(h->cfg.dtype, N, S, SW, h->classes, &hs, h->params + h->head_w_off, dl, last.g, hdw, hdb, &r,
+                                 h->ws + h->off_wslab, vk_head_multi_workspace_bytes(h->classes), st));
+        h->g_prereduced[h->decs[4].conv2] = 1;
+      } else {
         vk_bnr r = bnr_of(h, last);
         const bool fuse = !getenv("VK_NO_BNR_FUSION");
         const float* dl = dlogits ? dlogits : (const float*)(h->ws + h->off_dlogits);

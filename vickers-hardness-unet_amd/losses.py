@@ -6,7 +6,17 @@
 
 ``DiceLoss`` and ``BCEDiceLoss`` run the fused HIP reduction (vk_bce_dice_loss); both participate in
 autograd.  smp defaults restated: from_logits=True, smooth=0, eps=1e-7, log_loss=False, batch-global
-reduction."""
+reduction.
+
+``DiceLoss`` / ``BCEDiceLoss`` here are the reference's binary drop-ins and refuse other modes, as before.  More than one class
+(``vk.multiclass.Unet(classes=C)``, logits [N,C,H,W]) uses the subclasses in ``vk.multiclass``, which take every mode:
+
+    vk.multiclass.DiceLoss(mode="multilabel")  target fp32 [N,C,H,W]  sigmoid per channel      (vk_multilabel_loss)
+    vk.multiclass.DiceLoss(mode="multiclass")  target int64 [N,H,W]   softmax over channels    (vk_multiclass_loss)
+    vk.multiclass.BCEDiceLoss(mode="multilabel") = nn.BCEWithLogitsLoss() + DiceLoss("multilabel")
+    CEDiceLoss()                                 = nn.CrossEntropyLoss() + DiceLoss("multiclass")   (also vk.multiclass.CEDiceLoss)
+
+A multi-class label outside [0, C) raises VkError (the kernel reports it through a device flag that is read back)."""
 from __future__ import annotations
 
 import torch
@@ -41,20 +51,84 @@ class _LossFn(torch.autograd.Function):
         return (ctx.dl * g).to(ctx.in_dtype), None, None, None
 
 
+class _MultiLossFn(torch.autograd.Function):
+    """vk_multilabel_loss / vk_multiclass_loss on logits [N,C,H,W]: w_pix * (BCE or CE) + w_dice * Dice."""
+
+    @staticmethod
+    def forward(ctx, logits, target, multiclass, w_pix, w_dice):
+        if not logits.is_cuda:
+            raise VkError("loss input is on %s: no CPU fallback in this package" % logits.device)
+        if logits.dim() != 4:
+            raise ValueError("expected logits [N,C,H,W], got %s" % (tuple(logits.shape),))
+        N, Cc, H, W = logits.shape
+        x = logits.detach().contiguous().float()
+        if multiclass:
+            if tuple(target.shape) != (N, H, W) or target.dtype != torch.int64:
+                raise ValueError("DiceLoss('multiclass'): target must be int64 [N,H,W], got %s %s" % (target.dtype, tuple(target.shape)))
+            y = target.detach().contiguous()
+        else:
+            y = target.detach().float().expand_as(x).contiguous()
+        L = lib()
+        ws = torch.empty(L.vk_multi_loss_workspace_bytes(N, Cc, H * W), dtype=torch.uint8, device=x.device)
+        out = torch.empty(4, dtype=torch.float32, device=x.device)
+        dl = torch.empty_like(x) if logits.requires_grad else None
+        fn = L.vk_multiclass_loss if multiclass else L.vk_multilabel_loss
+        check(fn(N, Cc, H * W, x.data_ptr(), y.data_ptr(), ws.data_ptr(), ws.numel(), out.data_ptr(), _lib.ptr(dl), 1.0,
+                 float(w_pix), float(w_dice), _lib.current_stream()),
+              "vk_multiclass_loss" if multiclass else "vk_multilabel_loss")
+        if multiclass:
+            bad = int(out[3].item())          # the device flag of out-of-range labels (one host sync)
+            if bad:
+                raise VkError("multi-class target holds %d label(s) outside [0, %d)" % (bad, Cc))
+        ctx.dl = dl
+        ctx.in_dtype = logits.dtype
+        return out[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.dl is None:
+            return None, None, None, None, None
+        return (ctx.dl * g).to(ctx.in_dtype), None, None, None, None
+
+
 class DiceLoss(nn.Module):
+    modes = ("binary",)            # the reference's DiceLoss; vk.multiclass.DiceLoss adds "multilabel" and "multiclass"
+
     def __init__(self, mode: str = "binary", classes=None, log_loss: bool = False, from_logits: bool = True,
                  smooth: float = 0.0, ignore_index=None, eps: float = 1e-7):
         super().__init__()
-        if mode != "binary" or classes is not None or log_loss or not from_logits or smooth != 0.0 \
+        if mode not in self.modes or classes is not None or log_loss or not from_logits or smooth != 0.0 \
                 or ignore_index is not None or eps != 1e-7:
-            raise NotImplementedError("only DiceLoss(mode='binary') with smp defaults is implemented (reference train.py:601)")
+            raise NotImplementedError("only DiceLoss(mode=%s) with smp defaults is implemented (reference train.py:601)%s"
+                                      % (" | ".join(repr(m) for m in self.modes),
+                                         "" if len(self.modes) > 1 else "; more than one class: vk.multiclass.DiceLoss"))
+        self.mode = mode
 
     def forward(self, y_pred, y_true):
-        return _LossFn.apply(y_pred, y_true, 0.0, 1.0)
+        if self.mode == "binary":
+            return _LossFn.apply(y_pred, y_true, 0.0, 1.0)
+        return _MultiLossFn.apply(y_pred, y_true, self.mode == "multiclass", 0.0, 1.0)
 
 
 class BCEDiceLoss(nn.Module):
-    """``BCEWithLogitsLoss()(x, y) + DiceLoss('binary')(x, y)`` in one reduction pass."""
+    """``BCEWithLogitsLoss()(x, y) + DiceLoss(mode)(x, y)`` in one reduction pass; mode 'binary' here, also 'multilabel' in
+    vk.multiclass.BCEDiceLoss."""
+    modes = ("binary",)
+
+    def __init__(self, mode: str = "binary"):
+        super().__init__()
+        if mode not in self.modes:
+            raise NotImplementedError("BCEDiceLoss(mode=%r): %s" % (mode, " | ".join(repr(m) for m in self.modes)))
+        self.mode = mode
 
     def forward(self, y_pred, y_true):
-        return _LossFn.apply(y_pred, y_true, 1.0, 1.0)
+        if self.mode == "binary":
+            return _LossFn.apply(y_pred, y_true, 1.0, 1.0)
+        return _MultiLossFn.apply(y_pred, y_true, False, 1.0, 1.0)
+
+
+class CEDiceLoss(nn.Module):
+    """``CrossEntropyLoss()(x, t) + DiceLoss('multiclass')(x, t)`` in one reduction pass; t int64 [N,H,W] in [0, C)."""
+
+    def forward(self, y_pred, y_true):
+        return _MultiLossFn.apply(y_pred, y_true, True, 1.0, 1.0)

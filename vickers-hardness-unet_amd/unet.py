@@ -3,7 +3,7 @@ as the reference builds it (train.py:357-379 ``build_model``; infer_pth_gui.py:3
 ``Segmenter``), executed by the HIP engine in libvkunet.so.
 
 API surface kept: constructor arguments, ``forward(x[N,3,S,S] fp32) -> logits
-[N,1,S,S] fp32``, ``train()/eval()``, ``.to(device)``, ``parameters()``, ``state_dict()`` /
+[N,1,S,S] fp32`` (``vk.multiclass.Unet``: ``classes=C``, 1 <= C <= 16, logits [N,C,S,S]), ``train()/eval()``, ``.to(device)``, ``parameters()``, ``state_dict()`` /
 ``load_state_dict(strict=True)`` with smp's 278 keys (conv weights are logical OIHW tensors whose memory
 is KRSC = torch channels_last, all living in one flat fp32 buffer), autograd participation
 (``loss.backward()`` fills ``p.grad``), ``torch.autocast`` selects the 16-bit plan exactly where the
@@ -43,7 +43,8 @@ class _Plan:
         self.N, self.S, self.H, self.W, self.dtype, self.training = N, S, H, W, dtype, training
         cfg = _lib.vk_unet_config(N, H, _lib.dtype_code(dtype), 1 if training else 0, W)
         h = C.c_void_p()
-        check(L.vk_unet_create(C.byref(cfg), C.byref(h)), "vk_unet_create")
+        self.classes = model.classes
+        check(L.vk_unet_create_ex(C.byref(cfg), self.classes, C.byref(h)), "vk_unet_create_ex")
         self.h = h
         self.ws_bytes = L.vk_unet_workspace_bytes(h)
         dev = model._flat["params"].device
@@ -138,6 +139,8 @@ class _UnetFn(torch.autograd.Function):
 
 
 class Unet(nn.Module):
+    max_classes = 1                # the reference's binary model; vk.multiclass.Unet takes 1 <= classes <= 16
+
     def __init__(self, encoder_name: str = "resnet34", encoder_depth: int = 5, encoder_weights: Optional[str] = "imagenet",
                  decoder_use_batchnorm: bool = True, decoder_channels=(256, 128, 64, 32, 16),
                  decoder_attention_type: Optional[str] = None, in_channels: int = 3, classes: int = 1,
@@ -150,15 +153,22 @@ class Unet(nn.Module):
             raise VkError("encoder_weights=%r needs a checkpoint download; no network here — pass None and "
                           "load_state_dict() a checkpoint instead" % (encoder_weights,))
         if (encoder_depth != 5 or tuple(decoder_channels) != (256, 128, 64, 32, 16) or not decoder_use_batchnorm
-                or decoder_attention_type is not None or in_channels != 3 or classes != 1 or activation is not None
+                or decoder_attention_type is not None or in_channels != 3 or activation is not None
                 or aux_params is not None):
-            raise NotImplementedError("only in_channels=3, classes=1, activation=None, default decoder are implemented "
+            raise NotImplementedError("only in_channels=3, activation=None, default decoder are implemented "
                                       "(reference train.py:372-378)")
+        if not isinstance(classes, int) or not 1 <= classes <= self.max_classes:
+            if self.max_classes == 1:
+                raise NotImplementedError("classes=%r: vk.Unet is the reference's binary model (classes=1); more than one class: "
+                                          "vk.multiclass.Unet(classes=C), 1 <= C <= 16" % (classes,))
+            raise NotImplementedError("classes=%r: 1 <= classes <= %d is implemented (the head is one 16-wide tile of output "
+                                      "channels)" % (classes, self.max_classes))
+        self.classes = classes
         self.compute_dtype = compute_dtype
         L = lib()
         cfg = _lib.vk_unet_config(1, 32, _lib.VK_F32, 0)
         h = C.c_void_p()
-        check(L.vk_unet_create(C.byref(cfg), C.byref(h)), "vk_unet_create")
+        check(L.vk_unet_create_ex(C.byref(cfg), classes, C.byref(h)), "vk_unet_create_ex")
         try:
             self._table = []
             for i in range(L.vk_unet_num_tensors(h)):
@@ -381,7 +391,7 @@ class Unet(nn.Module):
         x = x.detach().contiguous().float()
         if training:
             plan.set_bn_frozen(self._bn_frozen_flags())      # per-layer BatchNorm modes; the engine keeps them for the backward
-        logits = torch.empty(plan.N, 1, plan.H, plan.W, dtype=torch.float32, device=x.device)
+        logits = torch.empty(plan.N, self.classes, plan.H, plan.W, dtype=torch.float32, device=x.device)
         check(L.vk_unet_forward(plan.h, x.data_ptr(), logits.data_ptr(), 1 if training else 0, st), "vk_unet_forward")
         plan._last_x = x      # keep the input alive until backward has consumed the plan's x4 copy
         return logits
@@ -478,21 +488,43 @@ class Unet(nn.Module):
 
     # ------------------------------------------------------------------ fused step (no autograd graph)
     def loss_and_backward(self, x: torch.Tensor, y: torch.Tensor, grad_scale: float = 1.0,
-                          dtype: Optional[torch.dtype] = None) -> torch.Tensor:
-        """forward (BatchNorm layers in their modules' modes) + BCE+Dice + backward in one call; the engine's loss kernel feeds the
-        head gradient directly.  Returns a device tensor [total, bce, dice] (no host sync).
+                          dtype: Optional[torch.dtype] = None, mode: Optional[str] = None) -> torch.Tensor:
+        """forward (BatchNorm layers in their modules' modes) + loss + backward in one call; the engine's loss kernel feeds the
+        head gradient directly.  Returns a device tensor [total, bce or ce, dice] (no host sync).
         Equivalent to train.py:436-448 ``logits = model(x); loss = bce + dice; loss.backward()``; ``requires_grad`` of the parameters
-        is read at this call (frozen ones get no gradient, see INTEGRATION.md "Fine-tuning")."""
+        is read at this call (frozen ones get no gradient, see INTEGRATION.md "Fine-tuning").
+        ``mode``: None / "binary" (classes == 1: BCEWithLogitsLoss + DiceLoss("binary")), "multilabel" (y fp32 [N,C,H,W]:
+        BCEWithLogitsLoss + DiceLoss("multilabel")) or "multiclass" (y int64 [N,H,W] in [0, C): CrossEntropyLoss +
+        DiceLoss("multiclass"); a label outside [0, C) makes the result NaN).  With classes > 1 the mode must be
+        given."""
+        if mode is None:
+            if self.classes != 1:
+                raise ValueError("loss_and_backward: classes=%d needs mode='multilabel' or mode='multiclass'" % self.classes)
+            mode = "binary"
+        codes = {"binary": _lib.VK_LOSS_BINARY, "multilabel": _lib.VK_LOSS_MULTILABEL, "multiclass": _lib.VK_LOSS_MULTICLASS}
+        if mode not in codes:
+            raise ValueError("loss_and_backward: unknown mode %r" % (mode,))
         self._check_input(x)
         mask = self._trainable_mask()
         if not any(mask):
             raise VkError("loss_and_backward: no parameter requires grad (every tensor is frozen)")
         N, _, H, W = x.shape
         plan = self.plan_for(N, H if H == W else (H, W), dtype or self.compute_dtype, True)
+        if mode == "multiclass" and (tuple(y.shape) != (N, H, W) or y.dtype != torch.int64):
+            raise ValueError("loss_and_backward(mode='multiclass'): target must be int64 [N,H,W], got %s %s" % (y.dtype, tuple(y.shape)))
         logits = self._run_forward(plan, x, True)
-        y = y.detach().contiguous().float()
-        check(lib().vk_unet_loss(plan.h, logits.data_ptr(), y.data_ptr(), plan.loss_out.data_ptr(), float(grad_scale),
-                                 1.0, 1.0, _lib.current_stream()), "vk_unet_loss")
+        if mode == "multiclass":
+            y = y.detach().contiguous()
+        elif mode == "multilabel":
+            y = y.detach().float().expand(N, self.classes, H, W).contiguous()
+        else:
+            y = y.detach().contiguous().float()
+        if mode == "binary":
+            check(lib().vk_unet_loss(plan.h, logits.data_ptr(), y.data_ptr(), plan.loss_out.data_ptr(), float(grad_scale),
+                                     1.0, 1.0, _lib.current_stream()), "vk_unet_loss")
+        else:
+            check(lib().vk_unet_loss_ex(plan.h, codes[mode], logits.data_ptr(), y.data_ptr(), plan.loss_out.data_ptr(),
+                                        float(grad_scale), 1.0, 1.0, _lib.current_stream()), "vk_unet_loss_ex")
         self._run_backward(plan, None, mask)
         self.last_logits = logits
         return plan.loss_out[:3]

@@ -13,6 +13,7 @@
  *   vk_unet_set_bn_frozen ..................... module.eval() of single BatchNorm layers inside a training forward
  *   vk_unet_set_input_grad .................... x.requires_grad_() (x.grad: saliency maps)
  *   vk_seg_metrics ............................ dice_coef / iou_coef (validate) train.py:230-281, 518-522
+ *   vk_seg_metrics_multi ...................... the same per class for Unet(classes=C): counts tp/fp/fn/tn, Dice / IoU per class
  *   vk_comm_* / vk_allreduce_bucket ........... (no reference counterpart: the 8-GPU data-parallel exchange)
  *   vk_adamw_step ............................. optimizer.step()/zero_grad   train.py:428, 449 (606)
  *   vk_amp_check_inf / vk_amp_unscale_check /
@@ -25,6 +26,8 @@
  *                                               ui_infer_quadrilateral.py:197-216, 662-678; ui_infer_rectangle.py:225-245, 520-535
  *   vk_letterbox_postprocess_mask ............. sigmoid, threshold, un-letterbox  infer_pth_gui.py:26-29, 50-53
  *   vk_letterbox_postprocess_prob ............. sigmoid, un-letterbox, clip       ui_infer_quadrilateral.py:219-231, 705-711
+ *   vk_letterbox_postprocess_labels / _mask_multi / _prob_multi  the same for C class planes: argmax label map, per-class masks,
+ *                                               per-class sigmoid or softmax probabilities
  *   vk_geom_minarearect ....................... postprocess_minarearect_multi      ui_infer_rectangle.py:291-381
  *   vk_geom_quadrilateral ..................... postprocess_minarearect_multi + robust_quadrilateral_from_contour  ui_infer_quadrilateral.py:262-530
  *   vk_letterbox_u8 / _mask_u8 / vk_augment_batch  VickersDataset.__getitem__ + albumentations pipeline  train.py:67-113, 173-200
@@ -235,6 +238,16 @@ int vk_letterbox_preprocess(const vk_letterbox_desc* d, const uint8_t* bgr, floa
 int vk_letterbox_postprocess_mask(const vk_letterbox_desc* d, const float* logits, float thresh, uint8_t* mask_hw, void* stream);
 /* logits [S][S] -> float32 [h][w] in [0,1]: sigmoid, crop, INTER_LINEAR back to the original size (copy when equal), clip */
 int vk_letterbox_postprocess_prob(const vk_letterbox_desc* d, const float* logits, float* prob_hw, void* stream);
+/* The same for a C-class logit map [C][S][S] (fp32 class planes, 1 <= C <= 16), same descriptor and arithmetic; with C == 1 the mask
+ * and multi-label probability calls give the bits of the two calls above.
+ * labels: argmax over the classes at the model's resolution (ties to the lowest index), crop, INTER_NEAREST -> uint8 [h][w]
+ * masks:  per class (sigmoid >= thresh) * 255, crop, INTER_NEAREST -> uint8 [C][h][w]
+ * probs:  mode VK_LOSS_MULTILABEL: per-class sigmoid; VK_LOSS_MULTICLASS (C >= 2): softmax over the classes (shift by the max, expf,
+ *         sum in class order, divide) at each source pixel; then crop, INTER_LINEAR (copy when equal), clip -> fp32 [C][h][w] */
+int vk_letterbox_postprocess_labels(const vk_letterbox_desc* d, int C, const float* logits, uint8_t* labels_hw, void* stream);
+int vk_letterbox_postprocess_mask_multi(const vk_letterbox_desc* d, int C, const float* logits, float thresh, uint8_t* masks_chw,
+                                        void* stream);
+int vk_letterbox_postprocess_prob_multi(const vk_letterbox_desc* d, int C, int mode, const float* logits, float* probs_chw, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Geometry post-processing of batched probability maps: what the reference's GUIs do with
@@ -448,6 +461,20 @@ int vk_multiclass_loss(int N, int C, int HW, const float* logits, const int64_t*
 size_t vk_seg_metrics_workspace_bytes(int n_images);
 int vk_seg_metrics(int n_images, size_t per_image, const float* pred, const float* target, int from_logits, float threshold,
                    float eps, void* workspace, size_t workspace_bytes, float* out, void* stream);
+/* The same per class for C = 1..16 class planes (multiclass_eval.hip).  mode VK_LOSS_MULTILABEL: logits fp32 [N][C][per_image],
+ * target fp32 [N][C][per_image] of 0/1, pred_c = (sigmoid(x_c) > threshold), or x_c > threshold when from_logits == 0; another target
+ * value skips that (pixel, class).  mode VK_LOSS_MULTICLASS (C >= 2): target int64 [N][per_image], pred = argmax_c x_c (ties to the
+ * lowest index; from_logits is irrelevant); a label outside [0, C) skips the pixel.  Skipped entries are counted in *bad_labels (device
+ * int, zeroed by the call); nothing faults.  Per (image, class): tp, fp, fn and tn = valid pixels - tp - fp - fn as int64 (exact,
+ * bit-reproducible); dice / iou as in vk_seg_metrics, so a class absent from both prediction and target scores 1; a class's batch
+ * score is the fp64 mean over images rounded once, the overall score the fp64 mean over classes.
+ * out (device floats, 2 + 2 C + 2 N C) = [mean dice, mean iou, dice_c[C], iou_c[C], per_image[N][C][2] {dice, iou}];
+ * stats (optional, device int64 [4][N][C]) = {tp, fp, fn, tn}.  With C == 1 and 0/1 targets, multilabel gives vk_seg_metrics's bits.
+ * workspace: vk_seg_metrics_multi_workspace_bytes(n_images, C) of 8-byte aligned device scratch. */
+size_t vk_seg_metrics_multi_workspace_bytes(int n_images, int C);
+int vk_seg_metrics_multi(int mode, int n_images, int C, size_t per_image, const float* logits, const void* target, int from_logits,
+                         float threshold, float eps, void* workspace, size_t workspace_bytes, int64_t* stats, float* out,
+                         int* bad_labels, void* stream);
 
 /* AdamW (decoupled decay) over a flat fp32 parameter buffer; optionally emits the 16-bit working copy.
  * inv_scale multiplies the gradient first (GradScaler unscale / data-parallel averaging).

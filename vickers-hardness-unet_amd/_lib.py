@@ -106,6 +106,9 @@ SIGNATURES = {
     "vk_letterbox_preprocess": (ci, [P(vk_letterbox_desc), vp, vp, vp]),
     "vk_letterbox_postprocess_mask": (ci, [P(vk_letterbox_desc), vp, cf, vp, vp]),
     "vk_letterbox_postprocess_prob": (ci, [P(vk_letterbox_desc), vp, vp, vp]),
+    "vk_letterbox_postprocess_labels": (ci, [P(vk_letterbox_desc), ci, vp, vp, vp]),
+    "vk_letterbox_postprocess_mask_multi": (ci, [P(vk_letterbox_desc), ci, vp, cf, vp, vp]),
+    "vk_letterbox_postprocess_prob_multi": (ci, [P(vk_letterbox_desc), ci, ci, vp, vp, vp]),
     "vk_geom_workspace_bytes": (i64, [P(vk_geom_desc), ci]),
     "vk_geom_minarearect": (ci, [P(vk_geom_desc), ci, vp, vp, vp, vp, vp, sz, vp]),
     "vk_geom_quadrilateral": (ci, [P(vk_geom_desc), ci, ci, vp, vp, vp, vp, vp, sz, vp]),
@@ -137,6 +140,8 @@ SIGNATURES = {
     "vk_multiclass_loss": (ci, [ci, ci, ci, vp, vp, vp, sz, vp, vp, cf, cf, cf, vp]),
     "vk_seg_metrics_workspace_bytes": (C.c_size_t, [ci]),
     "vk_seg_metrics": (ci, [ci, sz, vp, vp, ci, cf, cf, vp, sz, vp, vp]),
+    "vk_seg_metrics_multi_workspace_bytes": (sz, [ci, ci]),
+    "vk_seg_metrics_multi": (ci, [ci, ci, ci, sz, vp, vp, ci, cf, cf, vp, sz, vp, vp, vp, vp]),
     "vk_adamw_step": (ci, [sz, vp, vp, vp, vp, cf, cf, cf, cf, cf, ci, cf, vp, vp, ci, vp]),
     "vk_amp_check_inf": (ci, [sz, vp, vp, vp]),
     "vk_amp_unscale_check": (ci, [sz, vp, vp, vp, vp]),

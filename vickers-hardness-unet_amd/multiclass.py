@@ -8,14 +8,22 @@ other loss modes; the classes here are the same objects with the wider contract:
     loss = nn.CrossEntropyLoss()(logits, t) + dice(logits, t)         # t int64 [N,H,W]
     model.loss_and_backward(x, t, mode="multiclass")                  # the fused step
 
-The kernels are in csrc/multiclass.hip (vk_head_fwd_multi, vk_head_bwd_multi, vk_multilabel_loss, vk_multiclass_loss)."""
+The kernels are in csrc/multiclass.hip (vk_head_fwd_multi, vk_head_bwd_multi, vk_multilabel_loss, vk_multiclass_loss).
+
+Validation and inference (multiclass_eval.py: csrc/multiclass_eval.hip, csrc/multiclass_post.hip)::
+
+    mean_dice, mean_iou, dice_c, iou_c = vk.multiclass.seg_metrics(logits, t, mode="multiclass")
+    probs = vk.multiclass.Segmenter(model, mode="multiclass").infer(bgr)      # fp32 [C, h, w]"""
 from __future__ import annotations
 
 from . import losses as _losses
 from . import unet as _unet
 from .losses import CEDiceLoss  # noqa: F401
+from .multiclass_eval import (Segmenter, postprocess_labels, postprocess_masks, postprocess_probs, predict_mask,  # noqa: F401
+                              seg_metrics, seg_metrics_device, seg_stats)
 
-__all__ = ["Unet", "DiceLoss", "BCEDiceLoss", "CEDiceLoss"]
+__all__ = ["Unet", "DiceLoss", "BCEDiceLoss", "CEDiceLoss", "seg_stats", "seg_metrics_device", "seg_metrics", "postprocess_labels",
+           "postprocess_masks", "postprocess_probs", "predict_mask", "Segmenter"]
 
 
 class Unet(_unet.Unet):

@@ -177,6 +177,18 @@ typedef struct {
 int vk_conv_dgrad_fused(const vk_conv_desc* d, const void* w, void* y, void* y1, int split_k1, int pool2, const vk_bnr* bnr,
                         void* stream);
 
+/* Pointwise convolutions (R = S = 1, pad 0, stride 1 or 2; one source, no upsample): the Bottleneck conv1 / conv3 and the downsample
+ * shortcuts of the resnet50 encoder, as MFMA GEMMs over NHWC pixels (fp32: v_mfma_f32_16x16x4_f32).  VK_ERR_UNSUPPORTED for any other
+ * descriptor.  Channels (src0.C and K) are multiples of 4 (fp32) / 8 (16-bit); scale / shift 16-byte aligned.
+ * vk_conv1x1_fwd, transposed = 0: y[p][k] (+)= sum_c V[p*stride][c] * w[k][c], w [K][C]; stats as vk_conv_fwd's (caller zeroes).
+ *                transposed = 1: the data gradient, src0 = dz [N][H][W][src0.C] (H, W: the forward's output grid), K = the forward's
+ *                input channels, w = the transposed weights [K][src0.C] (vk_conv_fwd's data-gradient layout), y [N][Ho][Wo][K];
+ *                at stride 2 the pixels no tap reaches are written as zero, or left untouched with accumulate.
+ * vk_conv1x1_wgrad: dw[K][C] (fp32, +=) = sum_p dz[p][k] * V[p*stride][c], split over pixels with per-split partial tiles in
+ *                `workspace` (16-byte aligned; NULL or too small: one split) added up in a fixed order — same bits on every run. */
+int vk_conv1x1_fwd(const vk_conv_desc* d, const void* w, void* y, int accumulate, double* stats, void* stream);
+int vk_conv1x1_wgrad(const vk_conv_desc* d, const void* dz, float* dw, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Stem: 7x7 stride-2 pad-3 convolution of x4 [N][H][W][4] (channel 3 is zero padding) with packed
  * weights wp [64][7][32] (tap row r, 8 columns x 4 channels, zero padded). */
 int vk_stem_fwd(vk_dtype dtype, int N, int H, int W, const void* x4, const void* wp, void* y, double* stats,
@@ -544,6 +556,15 @@ int vk_unet_create(const vk_unet_config* cfg, vk_unet** out);
  * vk_unet_create is classes = 1 (the binary model: same kernels, launches and workspace as before). */
 int vk_unet_create_ex(const vk_unet_config* cfg, int classes, vk_unet** out);
 int vk_unet_num_classes(const vk_unet* h);
+/* smp.Unet(encoder_name=...) for the ResNet encoders the reference's config offers (train.py:357-379, 747-749): VK_ENC_RESNET18
+ * (BasicBlocks 2-2-2-2), VK_ENC_RESNET34 (3-4-6-3: vk_unet_create_ex, the same plan) and VK_ENC_RESNET50 (torchvision v1.5 Bottlenecks
+ * 3-4-6-3, expansion 4, its 1x1 layers on vk_conv1x1_*).  The tensor table, gradient buckets and the flag counts of
+ * vk_unet_set_trainable / vk_unet_set_bn_frozen follow the encoder (vk_unet_num_tensors, vk_unet_num_buckets). */
+#define VK_ENC_RESNET18 18
+#define VK_ENC_RESNET34 34
+#define VK_ENC_RESNET50 50
+int vk_unet_create_enc(const vk_unet_config* cfg, int classes, int encoder, vk_unet** out);
+int vk_unet_encoder(const vk_unet* h);
 void vk_unet_destroy(vk_unet* h);
 /* Optional: run a training plan's weight-gradient kernels on a second, library-owned HIP stream beside the caller's stream
  * (fork per layer once dz is final, join at the end of every backward stage, before the stage's gradient bucket may be

@@ -15,6 +15,7 @@ CSRC = PKG_DIR / "csrc"
 
 VK_F32, VK_BF16, VK_F16 = 0, 1, 2
 VK_LOSS_BINARY, VK_LOSS_MULTILABEL, VK_LOSS_MULTICLASS = 0, 1, 2
+VK_ENC_RESNET18, VK_ENC_RESNET34, VK_ENC_RESNET50 = 18, 34, 50
 
 
 class VkError(RuntimeError):
@@ -98,6 +99,8 @@ SIGNATURES = {
     "vk_conv_fwd_splitk": (ci, [P(vk_conv_desc), vp, vp, vp, sz, vp]),
     "vk_stem_fwd": (ci, [ci, ci, ci, ci, vp, vp, vp, vp, vp]),
     "vk_conv_wgrad": (ci, [P(vk_conv_desc), vp, vp, vp, sz, vp]),
+    "vk_conv1x1_fwd": (ci, [P(vk_conv_desc), vp, vp, ci, vp, vp]),
+    "vk_conv1x1_wgrad": (ci, [P(vk_conv_desc), vp, vp, vp, sz, vp]),
     "vk_conv_wgrad_batch_supports": (ci, [P(vk_conv_desc)]),
     "vk_conv_wgrad_batch": (ci, [P(vk_conv_desc), P(vp), P(vp), ci, ci, vp, sz, vp, sz, vp]),
     "vk_stem_wgrad": (ci, [ci, ci, ci, ci, vp, vp, vp, vp, sz, vp]),
@@ -151,6 +154,8 @@ SIGNATURES = {
     "vk_unet_create": (ci, [P(vk_unet_config), P(vp)]),
     "vk_unet_create_ex": (ci, [P(vk_unet_config), ci, P(vp)]),
     "vk_unet_num_classes": (ci, [vp]),
+    "vk_unet_create_enc": (ci, [P(vk_unet_config), ci, ci, P(vp)]),
+    "vk_unet_encoder": (ci, [vp]),
     "vk_unet_destroy": (None, [vp]),
     "vk_unet_set_side_stream": (ci, [vp, ci]),
     "vk_unet_num_tensors": (ci, [vp]),

@@ -17,6 +17,14 @@ static inline int grid_for(size_t work_items, int block = 256, int max_blocks = 
   return (int)b;
 }
 
+// Per-channel BatchNorm passes of layers wider than 512 channels (resnet50's block tails, up to 2048): a grid-stride loop keeps a
+// thread's channel group fixed only if grid * 256 is a multiple of the C / VE vectors of a pixel, so round the grid up to that.
+constexpr int kWideC = 2048;
+static inline int wide_grid(int blocks, int cv) {
+  const int m = cv > 256 ? cv / 256 : 1;          // cv is a power of two here (C in {1024, 2048})
+  return (blocks + m - 1) / m * m;
+}
+
 // ------------------------------------------------------------------------------------------------
 // K0: NCHW fp32 -> NHWC4 T
 template <typename T>
@@ -196,7 +204,7 @@ __global__ void k_maxpool_bwd(int N, int H, int W, int C, const T* __restrict__ 
 
 // ------------------------------------------------------------------------------------------------
 // K6: BasicBlock tail  out = relu(bn2(z) + shortcut)
-template <typename T>
+template <typename T, int MAXC>
 __global__ __launch_bounds__(256) void k_bn_add_relu(size_t pixels, int C, const T* __restrict__ z, const float* __restrict__ scale,
                                                      const float* __restrict__ shift, const T* __restrict__ res, const float* __restrict__ rscale,
                                                      const float* __restrict__ rshift, T* __restrict__ out) {
@@ -209,7 +217,7 @@ __global__ __launch_bounds__(256) void k_bn_add_relu(size_t pixels, int C, const
   const int c0 = (int)(t0 % CV) * VE;
   // per-workgroup coefficient table in LDS, one thread per channel: 32 scalar global loads per thread in this prologue cost
   // more than the whole tensor pass on the small (layer3/4) blocks (35 us floor per launch, measured)
-  __shared__ float cf[4][512];
+  __shared__ float cf[4][MAXC];
   for (int c = threadIdx.x; c < C; c += blockDim.x) {
     cf[0][c] = scale[c];
     cf[1][c] = shift[c];
@@ -432,6 +440,38 @@ __global__ __launch_bounds__(256) void k_bn_bwd_reduce(size_t pixels, int C, con
   }
 }
 
+// The same sums for layers wider than one 256-thread row of channel vectors (fp32, C > 1024: resnet50's 2048-wide block tails): every
+// thread owns channel vectors tid, tid + 256, ... for all of the block's pixels and adds its own channels' sums into the block's replica.
+template <typename T, int MASK>
+__global__ __launch_bounds__(256) void k_bn_bwd_reduce_wide(size_t pixels, int C, const T* __restrict__ dy, const T* __restrict__ z,
+                                                            const float* __restrict__ scale, const float* __restrict__ shift,
+                                                            const T* __restrict__ mask_src, double* sums) {
+  constexpr int VE = ElemTraits<T>::kVec;
+  const int CV = C / VE;
+  double* sp = sums + (size_t)(blockIdx.x % VK_STATS_REPLICAS) * 2 * C;
+  for (int cv = threadIdx.x; cv < CV; cv += blockDim.x) {
+    float sc[VE], sh[VE], s1[VE], s2[VE];
+#pragma unroll
+    for (int j = 0; j < VE; ++j) {
+      sc[j] = (MASK == 1) ? scale[cv * VE + j] : 1.f;
+      sh[j] = (MASK == 1) ? shift[cv * VE + j] : 0.f;
+      s1[j] = 0.f;
+      s2[j] = 0.f;
+    }
+    for (size_t p = blockIdx.x; p < pixels; p += gridDim.x) {
+      float g[VE], zf[VE];
+      masked_grad<T, MASK>(dy, z, mask_src, p * C + cv * VE, sc, sh, g, zf);
+#pragma unroll
+      for (int j = 0; j < VE; ++j) { s1[j] += g[j]; s2[j] += g[j] * zf[j]; }
+    }
+#pragma unroll
+    for (int j = 0; j < VE; ++j) {
+      atomicAdd(sp + cv * VE + j, (double)s1[j]);
+      atomicAdd(sp + C + cv * VE + j, (double)s2[j]);
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void k_bn_bwd_coeffs(int C, const double* __restrict__ sums, double count, const float* __restrict__ gamma,
                                                        const float* __restrict__ save_mean, const float* __restrict__ save_invstd, float* dgamma,
                                                        float* dbeta, float* coef) {
@@ -494,7 +534,7 @@ __global__ __launch_bounds__(256) void k_bn_bwd_coeffs_frozen(int C, const doubl
 // dz = a*g + b*z + c with (a, b, c) derived in-kernel from the reduction sums:
 //   dgamma = r*(S_gz - mu*S_g), dbeta = S_g, a = gamma*r, b = -gamma*r^2*dgamma/M, c = -a*dbeta/M - b*mu
 // Workgroup 0 also accumulates dgamma/dbeta into the flat gradient buffer (coef == nullptr: fused mode).
-template <typename T, int MASK>
+template <typename T, int MASK, int MAXC>
 __global__ __launch_bounds__(256) void k_bn_bwd_apply(size_t pixels, int C, const T* __restrict__ dy, const T* __restrict__ z,
                                                       const float* __restrict__ scale, const float* __restrict__ shift, const T* __restrict__ mask_src,
                                                       const float* __restrict__ coef, const double* __restrict__ sums, double count,
@@ -509,7 +549,7 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply(size_t pixels, int C, cons
   const size_t t0 = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
   const int c0 = (int)(t0 % CV) * VE;
   // per-workgroup coefficient table in LDS (one thread per channel), so the per-thread prologue is 3 LDS reads / channel
-  __shared__ float cf[3][512];
+  __shared__ float cf[3][MAXC];
   if (coef) {
     for (int c = threadIdx.x; c < C; c += blockDim.x) {
       cf[0][c] = coef[c];
@@ -1411,10 +1451,16 @@ extern "C" int vk_bn_add_relu(vk_dtype dtype, size_t pixels, int C, const void* 
   VK_CHECK_ARG(z && scale && shift && res && out && C % 8 == 0, "vk_bn_add_relu: bad argument");
   hipStream_t st = (hipStream_t)stream;
   vkh::ProfScope ps_("bn_add_relu", st, 0.0, (double)pixels * C * (dtype == VK_F32 ? 4.0 : 2.0) * 3.0);
-  VK_CHECK_ARG(C <= 512, "vk_bn_add_relu: C=%d unsupported", C);
-  // four vectors per thread (one unrolled pass) before the grid grows; the grid stays a multiple of C/VE threads
-  DISPATCH_T(dtype, hipLaunchKernelGGL(k_bn_add_relu<T>, dim3(grid_for((pixels * (C / ElemTraits<T>::kVec) + 3) / 4)), dim3(256), 0, st, pixels, C,
-                                       (const T*)z, scale, shift, (const T*)res, rscale, rshift, (T*)out));
+  VK_CHECK_ARG(C <= 512 || (C <= kWideC && (C & (C - 1)) == 0), "vk_bn_add_relu: C=%d unsupported", C);
+  // four vectors per thread (one unrolled pass) before the grid grows; the grid stays a multiple of C/VE threads.  Layers wider than
+  // 512 channels (resnet50's block tails) run an instance with a larger coefficient table; the others keep the 512-entry one
+  if (C <= 512) {
+    DISPATCH_T(dtype, hipLaunchKernelGGL((k_bn_add_relu<T, 512>), dim3(grid_for((pixels * (C / ElemTraits<T>::kVec) + 3) / 4)), dim3(256), 0, st,
+                                         pixels, C, (const T*)z, scale, shift, (const T*)res, rscale, rshift, (T*)out));
+  } else {
+    DISPATCH_T(dtype, hipLaunchKernelGGL((k_bn_add_relu<T, kWideC>), dim3(wide_grid(grid_for((pixels * (C / ElemTraits<T>::kVec) + 3) / 4), C / ElemTraits<T>::kVec)),
+                                         dim3(256), 0, st, pixels, C, (const T*)z, scale, shift, (const T*)res, rscale, rshift, (T*)out));
+  }
   VK_CHECK_HIP(hipGetLastError());
   return VK_OK;
 }
@@ -1423,6 +1469,17 @@ template <typename T>
 static int launch_bn_bwd_reduce(size_t pixels, int C, const void* dy, const void* z, int mask_mode, const float* scale,
                                 const float* shift, const void* mask_src, double* sums, hipStream_t st) {
   const int CV = C / ElemTraits<T>::kVec;
+  if (CV > 256) {              // fp32, C > 1024: one thread per channel vector cannot cover a pixel in one row pass
+    size_t nb = (pixels + 63) / 64;
+    if (nb > 512) nb = 512;
+    if (nb < 1) nb = 1;
+#define VK_RW(M) hipLaunchKernelGGL((k_bn_bwd_reduce_wide<T, M>), dim3((unsigned)nb), dim3(256), 0, st, pixels, C, (const T*)dy, (const T*)z, scale, shift, (const T*)mask_src, sums)
+    if (mask_mode == 0) VK_RW(0);
+    else if (mask_mode == 1) VK_RW(1);
+    else VK_RW(2);
+#undef VK_RW
+    return VK_OK;
+  }
   const int rows = 256 / CV;
   // every block ends with 2*C fp64 atomics, so give each at least 16 row passes
   size_t nb = (pixels + (size_t)rows * 16 - 1) / ((size_t)rows * 16);
@@ -1441,7 +1498,7 @@ extern "C" int vk_bn_bwd_reduce(vk_dtype dtype, size_t pixels, int C, const void
   VK_CHECK_ARG(mask_mode >= 0 && mask_mode <= 2, "vk_bn_bwd_reduce: mask_mode %d", mask_mode);
   VK_CHECK_ARG(mask_mode != 1 || (scale && shift), "vk_bn_bwd_reduce: mask_mode 1 needs scale/shift");
   VK_CHECK_ARG(mask_mode != 2 || mask_src, "vk_bn_bwd_reduce: mask_mode 2 needs mask_src");
-  VK_CHECK_ARG(C % 8 == 0 && C <= 512, "vk_bn_bwd_reduce: C=%d unsupported", C);
+  VK_CHECK_ARG(C % 8 == 0 && (C <= 512 || (C <= kWideC && (C & (C - 1)) == 0)), "vk_bn_bwd_reduce: C=%d unsupported", C);
   hipStream_t st = (hipStream_t)stream;
   vkh::ProfScope ps_("bn_bwd_reduce", st, 0.0, (double)pixels * C * (dtype == VK_F32 ? 4.0 : 2.0) * (mask_mode == 2 ? 3.0 : 2.0));
   DISPATCH_T(dtype, launch_bn_bwd_reduce<T>(pixels, C, dy, z, mask_mode, scale, shift, mask_src, sums, st));
@@ -1478,9 +1535,19 @@ struct BnApplyArgs {
 template <typename T>
 static int launch_bn_bwd_apply(const BnApplyArgs& a, hipStream_t st) {
   const int CV = a.C / ElemTraits<T>::kVec;
-  // grid * 256 must be a multiple of CV (<= 128): any block count works; keep enough blocks to fill the chip
-  dim3 grid(grid_for(a.pixels * CV / 2 + 1)), block(256);
-#define VK_APPLY(M) hipLaunchKernelGGL((k_bn_bwd_apply<T, M>), grid, block, 0, st, a.pixels, a.C, (const T*)a.dy, (const T*)a.z, a.scale, a.shift, \
+  // grid * 256 must be a multiple of CV (<= 128 up to 512 channels: any block count works); keep enough blocks to fill the chip
+  const bool wide = a.C > 512;
+  dim3 grid(wide ? wide_grid(grid_for(a.pixels * CV / 2 + 1), CV) : grid_for(a.pixels * CV / 2 + 1)), block(256);
+  if (wide) {
+#define VK_APPLY_W(M) hipLaunchKernelGGL((k_bn_bwd_apply<T, M, kWideC>), grid, block, 0, st, a.pixels, a.C, (const T*)a.dy, (const T*)a.z, a.scale, \
+    a.shift, (const T*)a.mask_src, a.coef, a.sums, a.count, a.gamma, a.mean, a.invstd, a.dgamma, a.dbeta, (T*)a.dz, (T*)a.g_out, a.g_acc)
+    if (a.mask_mode == 0) VK_APPLY_W(0);
+    else if (a.mask_mode == 1) VK_APPLY_W(1);
+    else VK_APPLY_W(2);
+#undef VK_APPLY_W
+    return VK_OK;
+  }
+#define VK_APPLY(M) hipLaunchKernelGGL((k_bn_bwd_apply<T, M, 512>), grid, block, 0, st, a.pixels, a.C, (const T*)a.dy, (const T*)a.z, a.scale, a.shift, \
     (const T*)a.mask_src, a.coef, a.sums, a.count, a.gamma, a.mean, a.invstd, a.dgamma, a.dbeta, (T*)a.dz, (T*)a.g_out, a.g_acc)
   if (a.mask_mode == 0) VK_APPLY(0);
   else if (a.mask_mode == 1) VK_APPLY(1);
@@ -1494,7 +1561,7 @@ static int bn_bwd_apply_common(vk_dtype dtype, const BnApplyArgs& a, void* strea
   VK_CHECK_ARG(a.mask_mode >= 0 && a.mask_mode <= 2, "vk_bn_bwd_apply: mask_mode %d", a.mask_mode);
   VK_CHECK_ARG(a.mask_mode != 1 || (a.scale && a.shift), "vk_bn_bwd_apply: mask_mode 1 needs scale/shift");
   VK_CHECK_ARG(a.mask_mode != 2 || a.mask_src, "vk_bn_bwd_apply: mask_mode 2 needs mask_src");
-  VK_CHECK_ARG(a.C <= 512 && a.C % 8 == 0, "vk_bn_bwd_apply: C=%d unsupported", a.C);
+  VK_CHECK_ARG(a.C % 8 == 0 && (a.C <= 512 || (a.C <= kWideC && (a.C & (a.C - 1)) == 0)), "vk_bn_bwd_apply: C=%d unsupported", a.C);
   hipStream_t st = (hipStream_t)stream;
   vkh::ProfScope ps_("bn_bwd_apply", st, 0.0, (double)a.pixels * a.C * (dtype == VK_F32 ? 4.0 : 2.0) * ((a.mask_mode == 2 ? 4.0 : 3.0) + (a.g_out ? (a.g_acc ? 2.0 : 1.0) : 0.0)));
   DISPATCH_T(dtype, launch_bn_bwd_apply<T>(a, st));

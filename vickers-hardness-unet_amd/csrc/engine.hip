@@ -345,6 +345,7 @@ struct ConvL {
   int bn;                 // following BN (-1 for the head)
   int Hin, Hout;          // spatial sizes: rows ...
   int Win, Wout;          // ... and columns (r04: H != W allowed, both divisible by 32)
+  bool pw = false;        // expanding 1x1 layer of a Bottleneck encoder: its data gradient runs on the 1x1 kernel (conv1x1.hip)
   int w_t = -1, b_t = -1; // parameter-tensor index (vk_unet_set_trainable order) of the weight / the bias (head only)
   int rank = 0;           // position of the weight in the backward order (assign_backward_ranks)
   // workspace
@@ -373,7 +374,8 @@ struct BnL {
 
 struct BlockL {
   int conv1, conv2, convd;      // convd = -1 for identity shortcut
-  int Cin, C, stride, Hin, Hout, Win, Wout;
+  int conv3 = -1;               // Bottleneck (resnet50): 1x1 expansion conv; -1 for a BasicBlock
+  int Cin, C, stride, Hin, Hout, Win, Wout;   // C: output channels (Bottleneck: 4 x its width)
   bool in_has_grad_first;       // gradient buffer of the block input was already written (skip feature)
   char* out = nullptr;
   char* gout = nullptr;
@@ -400,10 +402,33 @@ constexpr int kMaxStages = 16;
 constexpr int kMaxBatch = 40;                       // layers in one batched weight-gradient launch (the model has 35 of the class)
 constexpr size_t kEngineSlabBytes = 176u << 20;     // slab workspace of a training plan: partial tiles of a whole-backward batch (~950 x 147 KB)
 constexpr size_t kGradScratchFloats = 2048;         // frozen-gradient sink: dgamma [512] | dbeta [512] | head dw [144 C] | head db [C]
+constexpr int kMaxBnLayers = 64;                    // one bit per BatchNorm layer in the frozen-statistics masks (resnet50 has 63)
+
+// Encoder topology (smp.Unet(encoder_name=...) behind train.py:372, torchvision's ResNet layouts).  Backward stages: the blocks
+// [hi .. lo] each stage runs after the decoder's three stages, the last one with the stem; stage i completes gradient bucket i.
+struct EncoderTopo {
+  int code;
+  int nblocks[4];
+  bool bottleneck;
+  int nstages;
+  int stage_blocks[8][2];
+};
+static const EncoderTopo kEncoders[] = {
+    {VK_ENC_RESNET18, {2, 2, 2, 2}, false, 5, {{7, 7}, {6, 6}, {5, 4}, {3, 2}, {1, 0}}},
+    {VK_ENC_RESNET34, {3, 4, 6, 3}, false, 7, {{15, 15}, {14, 14}, {13, 13}, {12, 10}, {9, 7}, {6, 3}, {2, 0}}},
+    {VK_ENC_RESNET50, {3, 4, 6, 3}, true, 7, {{15, 15}, {14, 14}, {13, 13}, {12, 10}, {9, 7}, {6, 3}, {2, 0}}},
+};
+static const EncoderTopo* find_encoder(int code) {
+  for (const EncoderTopo& e : kEncoders)
+    if (e.code == code) return &e;
+  return nullptr;
+}
 
 struct vk_unet {
   vk_unet_config cfg;
   int classes = 1;               // output channels of the head (vk_unet_create_ex); 1 is the binary model and its kernels
+  const EncoderTopo* enc = nullptr;   // vk_unet_create_enc; resnet34 for vk_unet_create / vk_unet_create_ex
+  int sink_c = 512;              // gamma / beta slots of the frozen-gradient sink: the widest BatchNorm (resnet34 keeps 512)
   int eb;                        // element bytes of the activation dtype
   std::vector<vk_tensor_info> infos;
   int n_ptensors = 0;            // parameter tensors (kinds 0 and 1) in `infos`
@@ -493,7 +518,7 @@ float* grad_or_sink(vk_unet* h, int t, int64_t off, int sink_off) {
   return trains(h, t) ? h->grads + off : (float*)(h->ws + h->off_gscratch) + sink_off;
 }
 float* dgamma_of(vk_unet* h, const BnL& b) { return grad_or_sink(h, b.g_t, b.g_off, 0); }
-float* dbeta_of(vk_unet* h, const BnL& b) { return grad_or_sink(h, b.b_t, b.b_off, 512); }
+float* dbeta_of(vk_unet* h, const BnL& b) { return grad_or_sink(h, b.b_t, b.b_off, h->sink_c); }
 
 int add_info(vk_unet* h, const std::string& name, int kind, std::vector<int> dims, int64_t offset, int64_t numel) {
   vk_tensor_info ti;
@@ -559,8 +584,10 @@ void build_topology(vk_unet* h) {
   h->stem_conv = add_conv(h, "encoder.conv1", 3, 64, 7, 2, 3, S, SW);
   h->convs[h->stem_conv].bn = add_bn(h, "encoder.bn1", 64, cnt(S / 2, SW / 2));
   // --- encoder layers
-  const int nblocks[4] = {3, 4, 6, 3};
+  const EncoderTopo& E = *h->enc;
+  const int* nblocks = E.nblocks;
   const int planes[4] = {64, 128, 256, 512};
+  const int expansion = E.bottleneck ? 4 : 1;
   int inpl = 64, res = S / 4, resw = SW / 4;
   std::vector<int64_t> layer_start(4), layer3_mid(1);
   std::vector<int64_t> block_start;
@@ -571,28 +598,43 @@ void build_topology(vk_unet* h) {
       const int stride = (b == 0 && L > 0) ? 2 : 1;
       const std::string pre = "encoder.layer" + std::to_string(L + 1) + "." + std::to_string(b);
       BlockL blk;
-      blk.Cin = inpl; blk.C = planes[L]; blk.stride = stride; blk.Hin = res; blk.Hout = res / stride; blk.Win = resw; blk.Wout = resw / stride;
-      blk.conv1 = add_conv(h, pre + ".conv1", inpl, planes[L], 3, stride, 1, res, resw);
-      h->convs[blk.conv1].bn = add_bn(h, pre + ".bn1", planes[L], cnt(blk.Hout, blk.Wout));
-      blk.conv2 = add_conv(h, pre + ".conv2", planes[L], planes[L], 3, 1, 1, blk.Hout, blk.Wout);
-      h->convs[blk.conv2].bn = add_bn(h, pre + ".bn2", planes[L], cnt(blk.Hout, blk.Wout));
+      const int outc = planes[L] * expansion;
+      blk.Cin = inpl; blk.C = outc; blk.stride = stride; blk.Hin = res; blk.Hout = res / stride; blk.Win = resw; blk.Wout = resw / stride;
+      if (!E.bottleneck) {
+        blk.conv1 = add_conv(h, pre + ".conv1", inpl, planes[L], 3, stride, 1, res, resw);
+        h->convs[blk.conv1].bn = add_bn(h, pre + ".bn1", planes[L], cnt(blk.Hout, blk.Wout));
+        blk.conv2 = add_conv(h, pre + ".conv2", planes[L], planes[L], 3, 1, 1, blk.Hout, blk.Wout);
+        h->convs[blk.conv2].bn = add_bn(h, pre + ".bn2", planes[L], cnt(blk.Hout, blk.Wout));
+      } else {
+        // torchvision v1.5 Bottleneck: 1x1 reduce, 3x3 (carries the stride), 1x1 expand.  Data gradients of the expanding 1x1 layers
+        // (conv3, the shortcuts) run on conv1x1.hip, every other 1x1 pass on the generic kernels: measured faster that way
+        blk.conv1 = add_conv(h, pre + ".conv1", inpl, planes[L], 1, 1, 0, res, resw);
+        h->convs[blk.conv1].bn = add_bn(h, pre + ".bn1", planes[L], cnt(res, resw));
+        blk.conv2 = add_conv(h, pre + ".conv2", planes[L], planes[L], 3, stride, 1, res, resw);
+        h->convs[blk.conv2].bn = add_bn(h, pre + ".bn2", planes[L], cnt(blk.Hout, blk.Wout));
+        blk.conv3 = add_conv(h, pre + ".conv3", planes[L], outc, 1, 1, 0, blk.Hout, blk.Wout);
+        h->convs[blk.conv3].bn = add_bn(h, pre + ".bn3", outc, cnt(blk.Hout, blk.Wout));
+        h->convs[blk.conv3].pw = true;
+      }
       blk.convd = -1;
-      if (stride != 1 || inpl != planes[L]) {
-        blk.convd = add_conv(h, pre + ".downsample.0", inpl, planes[L], 1, stride, 0, res, resw);
-        h->convs[blk.convd].bn = add_bn(h, pre + ".downsample.1", planes[L], cnt(blk.Hout, blk.Wout));
+      if (stride != 1 || inpl != outc) {
+        blk.convd = add_conv(h, pre + ".downsample.0", inpl, outc, 1, stride, 0, res, resw);
+        h->convs[blk.convd].bn = add_bn(h, pre + ".downsample.1", outc, cnt(blk.Hout, blk.Wout));
+        h->convs[blk.convd].pw = E.bottleneck;        // resnet18 / resnet34 shortcuts keep the generic kernels (and their bits)
       }
       // the input of block 0 of layers 2-4 is a skip feature whose gradient the decoder wrote first
       blk.in_has_grad_first = (b == 0 && L > 0);
       h->blocks.push_back(blk);
-      inpl = planes[L];
+      inpl = outc;
       res = blk.Hout;
       resw = blk.Wout;
     }
     h->layer_last_block[L] = (int)h->blocks.size() - 1;
   }
-  // --- decoder
-  const int dec_in[5] = {512, 256, 128, 64, 32};
-  const int dec_skip[5] = {256, 128, 64, 64, 0};
+  // --- decoder (smp UnetDecoder: the deepest feature, then the skips f4, f3, f2, f1)
+  const int fch[4] = {planes[0] * expansion, planes[1] * expansion, planes[2] * expansion, planes[3] * expansion};
+  const int dec_in[5] = {fch[3], 256, 128, 64, 32};
+  const int dec_skip[5] = {fch[2], fch[1], fch[0], 64, 0};
   const int dec_out[5] = {256, 128, 64, 32, 16};
   std::vector<int64_t> dec_start(5);
   int dres = S / 32, dresw = SW / 32;
@@ -625,17 +667,16 @@ void build_topology(vk_unet* h) {
   }
   // --- gradient buckets in backward completion order (stage i completes bucket i)
   const int64_t P = h->n_params;
-  // block_start indices: layer1: 0..2, layer2: 3..6, layer3: 7..12, layer4: 13..15
+  // resnet34 / resnet50: block_start indices layer1: 0..2, layer2: 3..6, layer3: 7..12, layer4: 13..15 — buckets 3..9 are layer4.2,
+  // layer4.1, layer4.0, layer3.3-5, layer3.0-2, layer2, layer1 + stem
   h->buckets.push_back({dec_start[2], P});                       // stage 0: head + dec4 + dec3 + dec2
   h->buckets.push_back({dec_start[1], dec_start[2]});            // 1: dec1
   h->buckets.push_back({dec_start[0], dec_start[1]});            // 2: dec0
-  h->buckets.push_back({block_start[15], dec_start[0]});         // 3: layer4.2
-  h->buckets.push_back({block_start[14], block_start[15]});      // 4: layer4.1
-  h->buckets.push_back({block_start[13], block_start[14]});      // 5: layer4.0
-  h->buckets.push_back({block_start[10], block_start[13]});      // 6: layer3.3-5
-  h->buckets.push_back({block_start[7], block_start[10]});       // 7: layer3.0-2
-  h->buckets.push_back({block_start[3], block_start[7]});        // 8: layer2
-  h->buckets.push_back({0, block_start[3]});                     // 9: layer1 + stem
+  for (int s = 0; s < E.nstages; ++s) {
+    const int hi = E.stage_blocks[s][0], lo = E.stage_blocks[s][1];
+    const int64_t end = hi + 1 < (int)block_start.size() ? block_start[(size_t)hi + 1] : dec_start[0];
+    h->buckets.push_back({s + 1 == E.nstages ? 0 : block_start[(size_t)lo], end});
+  }
 }
 
 // Backward order of the parameter tensors (the order backward_stage visits them; the head's weight and bias share rank 0): a data
@@ -650,8 +691,17 @@ void assign_backward_ranks(vk_unet* h) {
     const DecL& d = h->decs[(size_t)i];
     bn(d.conv2); conv(d.conv2); bn(d.conv1); conv(d.conv1);
   }
-  for (int bi = 15; bi >= 0; --bi) {
+  for (int bi = (int)h->blocks.size() - 1; bi >= 0; --bi) {
     const BlockL& k = h->blocks[(size_t)bi];
+    if (k.conv3 >= 0) {             // Bottleneck, in backward_bottleneck's order
+      bn(k.conv3);
+      if (k.convd >= 0) bn(k.convd);
+      conv(k.conv3);
+      if (k.convd >= 0) conv(k.convd);
+      bn(k.conv2); conv(k.conv2);
+      bn(k.conv1); conv(k.conv1);
+      continue;
+    }
     bn(k.conv2);
     if (k.convd >= 0) bn(k.convd);
     conv(k.conv2);
@@ -676,7 +726,11 @@ void update_last_rank(vk_unet* h) {
 }
 
 // the frozen-gradient sink: dgamma [512] | dbeta [512] | head dw [144 C] | head db [C]; the binary model keeps its 2048 floats
-size_t grad_scratch_floats(const vk_unet* h) { return h->classes == 1 ? kGradScratchFloats : align_up(1024 + 145 * (size_t)h->classes, 64); }
+// other encoders: dgamma [sink_c] | dbeta [sink_c] | head dw [144 C] | head db [C], sink_c = the widest BatchNorm
+size_t grad_scratch_floats(const vk_unet* h) {
+  if (h->enc->code != VK_ENC_RESNET34) return align_up(2 * (size_t)h->sink_c + 145 * (size_t)h->classes, 64);
+  return h->classes == 1 ? kGradScratchFloats : align_up(1024 + 145 * (size_t)h->classes, 64);
+}
 
 void layout_workspace(vk_unet* h) {
   const int N = h->cfg.N, S = h->cfg.size, SW = h->cfg.width, eb = h->eb;
@@ -841,6 +895,10 @@ int finalize_bn(vk_unet* h, BnL& b, int training, hipStream_t st) {
                         h->bufs + b.rv_off, 1e-5f, 0.1f, b.scale, b.shift, b.mean, b.invstd, st);
 }
 
+// the data gradient of an expanding Bottleneck 1x1 layer on the pointwise kernel; VK_NO_CONV1X1=1 (read per launch, diagnostic): the
+// generic tap-by-tap kernel
+bool on_1x1(const ConvL& c) { return c.pw && !getenv("VK_NO_CONV1X1"); }
+
 int run_conv(vk_unet* h, ConvL& c, const vk_src& s0, const vk_src& s1, int training, hipStream_t st) {
   vk_conv_desc d = conv_desc(h, c, s0, s1);
   BnL& b = h->bns[c.bn];
@@ -888,7 +946,13 @@ extern "C" int vk_debug_hold_cus(int workgroups, int threads, int lds_bytes, int
 extern "C" int vk_unet_create(const vk_unet_config* cfg, vk_unet** out) { return vk_unet_create_ex(cfg, 1, out); }
 
 extern "C" int vk_unet_create_ex(const vk_unet_config* cfg, int classes, vk_unet** out) {
+  return vk_unet_create_enc(cfg, classes, VK_ENC_RESNET34, out);
+}
+
+extern "C" int vk_unet_create_enc(const vk_unet_config* cfg, int classes, int encoder, vk_unet** out) {
   VK_CHECK_ARG(cfg && out, "vk_unet_create: null argument");
+  const EncoderTopo* enc = find_encoder(encoder);
+  VK_CHECK_ARG(enc, "vk_unet_create_enc: encoder %d is not one of VK_ENC_RESNET18 / 34 / 50", encoder);
   VK_CHECK_ARG(classes >= 1 && classes <= 16, "vk_unet_create_ex: classes=%d is outside 1..16 (one 16-wide tile of head outputs)", classes);
   const int width = cfg->width > 0 ? cfg->width : cfg->size;
   VK_CHECK_ARG(cfg->N >= 1 && cfg->size >= 32 && cfg->size % 32 == 0 && width >= 32 && width % 32 == 0,
@@ -897,9 +961,17 @@ extern "C" int vk_unet_create_ex(const vk_unet_config* cfg, int classes, vk_unet
   vk_unet* h = new vk_unet();
   h->cfg = *cfg;
   h->classes = classes;
+  h->enc = enc;
   h->cfg.width = width;
   h->eb = cfg->dtype == VK_F32 ? 4 : 2;
   build_topology(h);
+  if (enc->code != VK_ENC_RESNET34)
+    for (const BnL& b : h->bns) h->sink_c = std::max(h->sink_c, b.C);
+  if ((int)h->bns.size() > kMaxBnLayers) {
+    delete h;
+    vkh::set_error("vk_unet_create_enc: more BatchNorm layers than the frozen-statistics mask holds");
+    return VK_ERR_ARG;
+  }
   assign_backward_ranks(h);
   layout_workspace(h);
   *out = h;
@@ -907,6 +979,7 @@ extern "C" int vk_unet_create_ex(const vk_unet_config* cfg, int classes, vk_unet
 }
 
 extern "C" int vk_unet_num_classes(const vk_unet* h) { return h ? h->classes : 0; }
+extern "C" int vk_unet_encoder(const vk_unet* h) { return h ? h->enc->code : 0; }
 
 extern "C" void vk_unet_destroy(vk_unet* h) {
   if (!h) return;
@@ -1086,7 +1159,7 @@ extern "C" int vk_unet_set_trainable(vk_unet* h, const uint8_t* flags, int n) {
 extern "C" int vk_unet_set_bn_frozen(vk_unet* h, const uint8_t* flags, int n) {
   VK_CHECK_ARG(h && flags, "vk_unet_set_bn_frozen: null argument");
   VK_CHECK_ARG(n == (int)h->bns.size(), "vk_unet_set_bn_frozen: %d flags for %d BatchNorm layers", n, (int)h->bns.size());
-  static_assert(sizeof(h->bn_frozen) * 8 >= 46, "one bit per BatchNorm layer");
+  static_assert(sizeof(h->bn_frozen) * 8 >= kMaxBnLayers, "one bit per BatchNorm layer");
   uint64_t m = 0;
   for (int l = 0; l < n; ++l) m |= (flags[l] ? 1ull : 0ull) << l;
   h->bn_frozen = m;
@@ -1152,23 +1225,27 @@ extern "C" int vk_unet_forward(vk_unet* h, const float* x, float* logits, int tr
     ConvL& c2 = h->convs[k.conv2];
     RET_IF(run_conv(h, c1, to_src(cur), null_src(), training, st));
     RET_IF(run_conv(h, c2, to_src(bn_act(h, c1)), null_src(), training, st));
-    const BnL& b2 = h->bns[c2.bn];
+    // Bottleneck: the block's tail reads conv3 where a BasicBlock's reads conv2
+    ConvL& ct = k.conv3 >= 0 ? h->convs[k.conv3] : c2;
+    if (k.conv3 >= 0) RET_IF(run_conv(h, ct, to_src(bn_act(h, c2)), null_src(), training, st));
+    const BnL& b2 = h->bns[ct.bn];
     const size_t pixels = (size_t)N * k.Hout * k.Wout;
     if (k.convd >= 0) {
       ConvL& cd = h->convs[k.convd];
       RET_IF(run_conv(h, cd, to_src(cur), null_src(), training, st));
       const BnL& bd = h->bns[cd.bn];
-      RET_IF(vk_bn_add_relu(dt, pixels, k.C, c2.z, b2.scale, b2.shift, cd.z, bd.scale, bd.shift, k.out, st));
+      RET_IF(vk_bn_add_relu(dt, pixels, k.C, ct.z, b2.scale, b2.shift, cd.z, bd.scale, bd.shift, k.out, st));
     } else {
-      RET_IF(vk_bn_add_relu(dt, pixels, k.C, c2.z, b2.scale, b2.shift, cur.ptr, nullptr, nullptr, k.out, st));
+      RET_IF(vk_bn_add_relu(dt, pixels, k.C, ct.z, b2.scale, b2.shift, cur.ptr, nullptr, nullptr, k.out, st));
     }
     cur = Act{k.out, k.C, nullptr, nullptr, 0};
   }
   // decoder
   Act skips[5];
-  skips[0] = Act{h->blocks[h->layer_last_block[2]].out, 256, nullptr, nullptr, 0};   // f4
-  skips[1] = Act{h->blocks[h->layer_last_block[1]].out, 128, nullptr, nullptr, 0};   // f3
-  skips[2] = Act{h->blocks[h->layer_last_block[0]].out, 64, nullptr, nullptr, 0};    // f2
+  for (int i = 0; i < 3; ++i) {                                                        // f4, f3, f2
+    const BlockL& fb = h->blocks[h->layer_last_block[2 - i]];
+    skips[i] = Act{fb.out, fb.C, nullptr, nullptr, 0};
+  }
   skips[3] = bn_act(h, stem);                                                         // f1 = relu(bn1(conv1 x))
   skips[4] = Act{nullptr, 0, nullptr, nullptr, 0};
   Act xd = cur;   // f5
@@ -1323,6 +1400,10 @@ vk_conv_desc dgrad_desc(vk_unet* h, ConvL& c) {
 // cover the shape; *fused tells the caller whether that happened
 int conv_dgrad_into(vk_unet* h, ConvL& c, ConvL& into, bool* fused, hipStream_t st) {
   vk_conv_desc d = dgrad_desc(h, c);
+  if (on_1x1(c)) {
+    *fused = false;
+    return vk_conv1x1_fwd(&d, dgrad_weights(h, c), into.g, 0, nullptr, st);
+  }
   vk_bnr r = bnr_of(h, into);
   int rc = getenv("VK_NO_BNR_FUSION") ? VK_ERR_UNSUPPORTED : vk_conv_dgrad_fused(&d, dgrad_weights(h, c), into.g, nullptr, 0, 0, &r, st);
   *fused = rc == VK_OK;
@@ -1341,6 +1422,7 @@ int conv_dgrad(vk_unet* h, ConvL& c, void* y, void* y1, int split, int accumulat
   s.ptr = c.g; s.C = c.K; s.up = 0; s.scale = nullptr; s.shift = nullptr; s.relu = 0;
   d.src0 = s;
   d.src1 = null_src();
+  if (on_1x1(c) && !split) return vk_conv1x1_fwd(&d, dgrad_weights(h, c), y, accumulate, nullptr, st);
   if (c.halo_dg) return vk_conv_fwd_packed(&d, dgrad_weights(h, c), y, y1, split, accumulate, nullptr, st);
   return vk_conv_fwd(&d, dgrad_weights(h, c), y, y1, split, accumulate, nullptr, st);
 }
@@ -1356,7 +1438,7 @@ int backward_decoder(vk_unet* h, int i, hipStream_t st) {
   void* g_prev;       // gradient buffer of the upsampled input (low resolution)
   if (i == 0) {
     BlockL& f5 = h->blocks[h->layer_last_block[3]];
-    xprev = Act{f5.out, 512, nullptr, nullptr, 0};
+    xprev = Act{f5.out, f5.C, nullptr, nullptr, 0};
     g_prev = f5.gout;
   } else {
     ConvL& pc2 = h->convs[h->decs[i - 1].conv2];
@@ -1489,6 +1571,67 @@ int backward_block(vk_unet* h, int bi, hipStream_t st) {
   return trains(h, c1.w_t) ? conv_wgrad(h, c1, to_src(xin), null_src(), st) : VK_OK;
 }
 
+// resnet50's Bottleneck, out = relu(bn3(conv3(relu(bn2(conv2(relu(bn1(conv1 x))))))) + shortcut) (reference: torchvision
+// Bottleneck.forward behind train.py:436; autograd's backward nodes behind :443 / :448).  Unfused BatchNorm backward passes except
+// where conv2's data gradient covers bn1's reduce (vk_bnr on the 3x3 tile kernels); the block input gradient is the sum of conv1's
+// and the shortcut's data gradients.
+int backward_bottleneck(vk_unet* h, int bi, hipStream_t st) {
+  BlockL& k = h->blocks[bi];
+  ConvL& c1 = h->convs[k.conv1];
+  ConvL& c2 = h->convs[k.conv2];
+  ConvL& c3 = h->convs[k.conv3];
+  BnL& b3 = h->bns[c3.bn];
+  const vk_dtype dt = h->cfg.dtype;
+  const size_t pixels = (size_t)h->cfg.N * k.Hout * k.Wout;
+  h->tail_prereduced[(size_t)bi] = 0;
+  if (!need_from(h, b3.rank)) return VK_OK;          // frozen from here on (vk_unet_set_trainable)
+  Act xin;
+  void* gin;
+  if (bi == 0) {
+    xin = Act{h->ws + h->off_pool, 64, nullptr, nullptr, 0};
+    gin = h->ws + h->off_gpool;
+  } else {
+    BlockL& pb = h->blocks[bi - 1];
+    xin = Act{pb.out, pb.C, nullptr, nullptr, 0};
+    gin = pb.gout;
+  }
+  // tail: g = gout * [out > 0] -> dz3 (and dzd, or gin (+)= g through the identity shortcut)
+  bool gin_written = k.in_has_grad_first;
+  if (bn_sums_needed(h, b3)) RET_IF(vk_bn_bwd_reduce(dt, pixels, k.C, k.gout, c3.z, 2, nullptr, nullptr, k.out, b3.bsums, st));
+  if (k.convd < 0) {
+    RET_IF(bn_bwd_phase2(h, b3, k.C, pixels, k.gout, c3.z, 2, k.out, c3.g, gin, gin_written ? 1 : 0, st));
+    gin_written = true;
+  } else {
+    RET_IF(bn_bwd_phase2(h, b3, k.C, pixels, k.gout, c3.z, 2, k.out, c3.g, nullptr, 0, st));
+    ConvL& cd = h->convs[k.convd];
+    BnL& bd = h->bns[cd.bn];
+    if (need_from(h, bd.rank)) {
+      if (bn_sums_needed(h, bd)) RET_IF(vk_bn_bwd_reduce(dt, pixels, k.C, k.gout, cd.z, 2, nullptr, nullptr, k.out, bd.bsums, st));
+      RET_IF(bn_bwd_phase2(h, bd, k.C, pixels, k.gout, cd.z, 2, k.out, cd.g, nullptr, 0, st));
+    }
+  }
+  // conv3: data gradient into conv2's gradient buffer (w.r.t. relu(bn2(z2))), then its weight gradient
+  const bool into2 = need_from(h, h->bns[c2.bn].rank);
+  if (into2) RET_IF(conv_dgrad(h, c3, c2.g, nullptr, 0, 0, st));
+  if (trains(h, c3.w_t)) RET_IF(conv_wgrad(h, c3, to_src(bn_act(h, c2)), null_src(), st));
+  if (k.convd >= 0 && trains(h, h->convs[k.convd].w_t)) RET_IF(conv_wgrad(h, h->convs[k.convd], to_src(xin), null_src(), st));
+  if (!into2) return VK_OK;
+  // conv2 (3x3, carries the stride)
+  RET_IF(bn_relu_bwd_inplace(h, c2, false, st));
+  const bool into1 = need_from(h, h->bns[c1.bn].rank);
+  bool fused1 = false;
+  if (into1) RET_IF(conv_dgrad_into(h, c2, c1, &fused1, st));
+  if (trains(h, c2.w_t)) RET_IF(conv_wgrad(h, c2, to_src(bn_act(h, c1)), null_src(), st));
+  if (!into1) return VK_OK;
+  // conv1 and the shortcut: both data gradients add into gin (the first writer stores)
+  RET_IF(bn_relu_bwd_inplace(h, c1, fused1, st));
+  if (need_from(h, c1.rank + 1)) {
+    RET_IF(conv_dgrad(h, c1, gin, nullptr, 0, gin_written ? 1 : 0, st));
+    if (k.convd >= 0) RET_IF(conv_dgrad(h, h->convs[k.convd], gin, nullptr, 0, 1, st));
+  }
+  return trains(h, c1.w_t) ? conv_wgrad(h, c1, to_src(xin), null_src(), st) : VK_OK;
+}
+
 // the stem BatchNorm's coefficients (and gamma / beta gradients) from the sums vk_maxpool_bwd_bn_reduce left; a frozen layer has
 // (a, 0, 0) since the forward and runs the launch only for trainable gamma / beta
 int stem_coeffs(vk_unet* h, BnL& b, hipStream_t st) {
@@ -1589,8 +1732,8 @@ int backward_stage(vk_unet* h, const float* dlogits, int stage, hipStream_t st) 
       VK_CHECK_HIP(hipMemsetAsync(h->ws + h->off_bsums, 0, h->stats_bytes, st));
       ConvL& last = h->convs[h->decs[4].conv2];
       const ConvL& head = h->convs[h->head_conv];
-      float* const hdw = grad_or_sink(h, head.w_t, h->head_w_off, 1024);
-      float* const hdb = grad_or_sink(h, head.b_t, h->head_b_off, 1024 + 144 * h->classes);
+      float* const hdw = grad_or_sink(h, head.w_t, h->head_w_off, 2 * h->sink_c);
+      float* const hdb = grad_or_sink(h, head.b_t, h->head_b_off, 2 * h->sink_c + 144 * h->classes);
       vk_src hs = to_src(bn_act(h, last));
       if (h->classes > 1) {
         vk_bnr r = bnr_of(h, last);
@@ -1614,24 +1757,16 @@ int backward_stage(vk_unet* h, const float* dlogits, int stage, hipStream_t st) 
     }
     case 1: return backward_decoder(h, 1, st);
     case 2: return backward_decoder(h, 0, st);
-    case 3: return backward_block(h, 15, st);
-    case 4: return backward_block(h, 14, st);
-    case 5: return backward_block(h, 13, st);
-    case 6:
-      for (int b = 12; b >= 10; --b) RET_IF(backward_block(h, b, st));
-      return VK_OK;
-    case 7:
-      for (int b = 9; b >= 7; --b) RET_IF(backward_block(h, b, st));
-      return VK_OK;
-    case 8:
-      for (int b = 6; b >= 3; --b) RET_IF(backward_block(h, b, st));
-      return VK_OK;
-    case 9:
-      for (int b = 2; b >= 0; --b) RET_IF(backward_block(h, b, st));
-      return backward_stem(h, st);
   }
-  vkh::set_error("vk_unet_backward: bad stage %d", stage);
-  return VK_ERR_ARG;
+  // encoder stages from the topology table: blocks hi .. lo, the last stage ends with the stem
+  const int es = stage - 3;
+  if (es < 0 || es >= h->enc->nstages) {
+    vkh::set_error("vk_unet_backward: bad stage %d", stage);
+    return VK_ERR_ARG;
+  }
+  for (int b = h->enc->stage_blocks[es][0]; b >= h->enc->stage_blocks[es][1]; --b)
+    RET_IF(h->blocks[(size_t)b].conv3 >= 0 ? backward_bottleneck(h, b, st) : backward_block(h, b, st));
+  return es + 1 == h->enc->nstages ? backward_stem(h, st) : VK_OK;
 }
 
 }  // namespace

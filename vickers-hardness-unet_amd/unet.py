@@ -44,7 +44,7 @@ class _Plan:
         cfg = _lib.vk_unet_config(N, H, _lib.dtype_code(dtype), 1 if training else 0, W)
         h = C.c_void_p()
         self.classes = model.classes
-        check(L.vk_unet_create_ex(C.byref(cfg), self.classes, C.byref(h)), "vk_unet_create_ex")
+        model._create_handle(cfg, h)
         self.h = h
         self.ws_bytes = L.vk_unet_workspace_bytes(h)
         dev = model._flat["params"].device
@@ -140,6 +140,7 @@ class _UnetFn(torch.autograd.Function):
 
 class Unet(nn.Module):
     max_classes = 1                # the reference's binary model; vk.multiclass.Unet takes 1 <= classes <= 16
+    encoders = ("resnet34",)       # the reference's encoder; vk.encoders.Unet also builds resnet18 and resnet50
 
     def __init__(self, encoder_name: str = "resnet34", encoder_depth: int = 5, encoder_weights: Optional[str] = "imagenet",
                  decoder_use_batchnorm: bool = True, decoder_channels=(256, 128, 64, 32, 16),
@@ -147,8 +148,10 @@ class Unet(nn.Module):
                  activation: Optional[str] = None, aux_params: Optional[dict] = None, *,
                  compute_dtype: torch.dtype = torch.float32):
         super().__init__()
-        if encoder_name != "resnet34":
-            raise NotImplementedError("only the reference's configuration encoder_name='resnet34' is implemented")
+        if encoder_name not in self.encoders:
+            if self.encoders == ("resnet34",):
+                raise NotImplementedError("only the reference's configuration encoder_name='resnet34' is implemented")
+            raise NotImplementedError("encoder_name=%r: one of %s is implemented" % (encoder_name, ", ".join(self.encoders)))
         if encoder_weights is not None:
             raise VkError("encoder_weights=%r needs a checkpoint download; no network here — pass None and "
                           "load_state_dict() a checkpoint instead" % (encoder_weights,))
@@ -164,11 +167,12 @@ class Unet(nn.Module):
             raise NotImplementedError("classes=%r: 1 <= classes <= %d is implemented (the head is one 16-wide tile of output "
                                       "channels)" % (classes, self.max_classes))
         self.classes = classes
+        self.encoder_name = encoder_name
         self.compute_dtype = compute_dtype
         L = lib()
         cfg = _lib.vk_unet_config(1, 32, _lib.VK_F32, 0)
         h = C.c_void_p()
-        check(L.vk_unet_create_ex(C.byref(cfg), classes, C.byref(h)), "vk_unet_create_ex")
+        self._create_handle(cfg, h)
         try:
             self._table = []
             for i in range(L.vk_unet_num_tensors(h)):
@@ -198,6 +202,14 @@ class Unet(nn.Module):
         self._default_init()
 
     # ------------------------------------------------------------------ structure
+    def _create_handle(self, cfg, h):
+        """Engine plan of this model's encoder and classes (vk_unet_create_ex: resnet34; vk_unet_create_enc: the others)."""
+        if self.encoder_name == "resnet34":
+            check(lib().vk_unet_create_ex(C.byref(cfg), self.classes, C.byref(h)), "vk_unet_create_ex")
+        else:
+            code = {"resnet18": _lib.VK_ENC_RESNET18, "resnet50": _lib.VK_ENC_RESNET50}[self.encoder_name]
+            check(lib().vk_unet_create_enc(C.byref(cfg), self.classes, code, C.byref(h)), "vk_unet_create_enc")
+
     def _view(self, kind: int, dims: List[int], off: int, numel: int, which: str = "params") -> torch.Tensor:
         if kind == 0:
             K, Cc, R, S = dims
@@ -276,21 +288,22 @@ class Unet(nn.Module):
             enc = [t for t in self._table if t[1] == 0 and t[0].startswith("encoder.")]
             dec = [t for t in self._table if t[1] == 0 and t[0].startswith("decoder.")]
             head = [t for t in self._table if t[1] == 0 and t[0].startswith("segmentation_head.")][0]
-            # torchvision constructs conv1, then per block conv1, conv2, (downsample) — but the
+            # torchvision constructs conv1, then per block conv1, conv2 (, conv3 in a Bottleneck), (downsample) — but the
             # downsample conv is built BEFORE the block in _make_layer
             def ctor_order(ts):
-                out, i = [], 0
-                while i < len(ts):
-                    if i + 2 < len(ts) and ".downsample.0" in ts[i + 2][0]:
-                        out += [ts[i + 2], ts[i], ts[i + 1]]
-                        i += 3
-                    else:
-                        out.append(ts[i])
-                        i += 1
+                out, block = [], []
+                for t in ts + [("", 0, [], 0, 0)]:
+                    parts = t[0].split(".")
+                    prefix = ".".join(parts[:3]) if len(parts) > 3 and parts[1].startswith("layer") else t[0]
+                    if block and (not t[0] or prefix != block[0][0]):
+                        out += [b[1] for b in block if ".downsample." in b[1][0]] + [b[1] for b in block if ".downsample." not in b[1][0]]
+                        block = []
+                    if t[0]:
+                        block.append((prefix, t))
                 return out
             for t in ctor_order(enc):
                 ctor_draw(t[2])
-            ctor_draw([1000, 512], bias=True)                  # the fc layer torchvision builds and smp deletes
+            ctor_draw([1000, enc[-1][2][0]], bias=True)        # the fc layer torchvision builds and smp deletes (512 x expansion inputs)
             for t in enc:                                      # ResNet.__init__ init loop (module order)
                 w = torch.empty(t[2])
                 nn.init.kaiming_normal_(w, mode="fan_out", nonlinearity="relu")

@@ -364,7 +364,8 @@ int vk_input_transform(vk_dtype dtype, int N, int H, int W, const float* x, void
 
 /* BatchNorm statistics -> per-channel affine.  train=1: from batch sums stats[VK_STATS_REPLICAS][2][C] (count = N*H*W), updates
  * running stats (momentum 0.1, unbiased var) and writes mean/invstd for backward.  train=0: from
- * running stats.  scale = gamma*invstd, shift = beta - mean*scale. */
+ * running stats.  scale = gamma*invstd, shift = beta - mean*scale.  Any C > 0.  In train mode running_mean and running_var are
+ * given together or both NULL (nothing to update); count = 1 leaves the variance unscaled. */
 int vk_bn_finalize(int C, int train, const double* stats, double count, const float* gamma, const float* beta,
                    float* running_mean, float* running_var, float eps, float momentum, float* scale, float* shift,
                    float* save_mean, float* save_invstd, void* stream);
@@ -377,17 +378,23 @@ int vk_maxpool_bwd(vk_dtype dtype, int N, int H, int W, int C, const void* dpool
                    void* stream);
 /* vk_maxpool_bwd and the BatchNorm+ReLU-backward reduce of the tensor under the pool in one pass (stem tail): dy holds the other
  * gradient contributions on entry and g = (dy + maxpool backward) * [relu(z*scale+shift) > 0] on return; sum(g), sum(g*z) are added
- * into sums [VK_STATS_REPLICAS][2][C].  Phase 2 is vk_bn_bwd_apply with mask_mode 0. */
+ * into sums [VK_STATS_REPLICAS][2][C].  Phase 2 is vk_bn_bwd_apply with mask_mode 0.  C / 4 (fp32) or C / 8 (16-bit) must divide
+ * 256, else VK_ERR_ARG with dy and sums untouched (vk_bn_relu_maxpool and vk_maxpool_bwd take any C % 8 == 0). */
 int vk_maxpool_bwd_bn_reduce(vk_dtype dtype, int N, int H, int W, int C, const void* dpool, const uint8_t* argmax, const void* z,
                              const float* scale, const float* shift, void* dy, double* sums, void* stream);
 
-/* out = relu(z*scale+shift + (res*rscale+rshift | res)) — BasicBlock tail */
+/* out = relu(z*scale+shift + (res*rscale+rshift | res)) — BasicBlock tail.
+ * C: a multiple of 8 up to 512, or 1024 / 2048.  Any other multiple of 8 returns VK_ERR_UNSUPPORTED, a count that is not a positive
+ * multiple of 8 VK_ERR_ARG; both before anything touches the stream (out untouched). */
 int vk_bn_add_relu(vk_dtype dtype, size_t pixels, int C, const void* z, const float* scale, const float* shift,
                    const void* res, const float* rscale, const float* rshift, void* out, void* stream);
 
 /* BatchNorm(+ReLU) backward, two phases.  mask_mode 0: none, 1: relu(z*scale+shift) > 0, 2: mask_src > 0.
  * phase 1: sums double[VK_STATS_REPLICAS][2][C] += { sum g, sum g*z } (spread over the replicas),  g = dy * mask.
- * phase 2 (after vk_bn_bwd_coeffs): dz = a*g + b*z + c ; optional g_out (+)= g  (identity shortcut). */
+ * phase 2 (after vk_bn_bwd_coeffs): dz = a*g + b*z + c ; optional g_out (+)= g  (identity shortcut); dz may be dy (in place).
+ * C of vk_bn_bwd_reduce, vk_bn_bwd_apply and vk_bn_bwd_apply_fused: a multiple of 8 up to 512, or 1024 / 2048.  Any other multiple
+ * of 8 returns VK_ERR_UNSUPPORTED, a count that is not a positive multiple of 8 VK_ERR_ARG; both before anything touches the stream
+ * (sums / dz / g_out / dgamma / dbeta untouched).  vk_bn_bwd_coeffs[_frozen]: any C > 0. */
 int vk_bn_bwd_reduce(vk_dtype dtype, size_t pixels, int C, const void* dy, const void* z, int mask_mode,
                      const float* scale, const float* shift, const void* mask_src, double* sums, void* stream);
 int vk_bn_bwd_coeffs(int C, const double* sums, double count, const float* gamma, const float* save_mean,
@@ -400,7 +407,7 @@ int vk_bn_bwd_apply(vk_dtype dtype, size_t pixels, int C, const void* dy, const 
 int vk_bn_bwd_coeffs_frozen(int C, const double* sums, const float* gamma, const float* running_mean, const float* running_invstd,
                             float* dgamma, float* dbeta, float* coef_abc, void* stream);
 /* phase 2 with vk_bn_bwd_coeffs folded in: coefficients are derived from `sums` inside the kernel and
- * dgamma/dbeta are accumulated by it (one launch less per BatchNorm layer). */
+ * dgamma/dbeta are accumulated by it, once (one launch less per BatchNorm layer).  C as vk_bn_bwd_apply. */
 int vk_bn_bwd_apply_fused(vk_dtype dtype, size_t pixels, int C, const void* dy, const void* z, int mask_mode,
                           const float* scale, const float* shift, const void* mask_src, const double* sums, double count,
                           const float* gamma, const float* save_mean, const float* save_invstd, float* dgamma, float* dbeta,

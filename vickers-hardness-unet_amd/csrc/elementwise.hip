@@ -17,11 +17,15 @@ static inline int grid_for(size_t work_items, int block = 256, int max_blocks = 
   return (int)b;
 }
 
-// Per-channel BatchNorm passes of layers wider than 512 channels (resnet50's block tails, up to 2048): a grid-stride loop keeps a
-// thread's channel group fixed only if grid * 256 is a multiple of the C / VE vectors of a pixel, so round the grid up to that.
+// Channel-group invariant of the flat per-channel passes (k_bn_add_relu, k_bn_bwd_apply): a thread fixes its channel group once and
+// then walks a grid-stride loop, which keeps that group only if grid * 256 is a multiple of the CV = C / VE vectors of a pixel.  So the
+// grid is rounded up to a multiple of CV / gcd(CV, 256): 1 for every power-of-two CV up to 256 (the grid of the encoders' layers up to
+// 512 channels is what grid_for gives), CV / 256 above (resnet50's 1024 / 2048-wide block tails), the odd part of CV otherwise.
 constexpr int kWideC = 2048;
-static inline int wide_grid(int blocks, int cv) {
-  const int m = cv > 256 ? cv / 256 : 1;          // cv is a power of two here (C in {1024, 2048})
+static inline int channel_grid(int blocks, int cv) {
+  int g = cv, r = 256;
+  while (r) { const int t = g % r; g = r; r = t; }
+  const int m = cv / g;
   return (blocks + m - 1) / m * m;
 }
 
@@ -385,8 +389,8 @@ __global__ __launch_bounds__(256) void k_bn_bwd_reduce(size_t pixels, int C, con
                                                        const float* __restrict__ scale, const float* __restrict__ shift,
                                                        const T* __restrict__ mask_src, double* sums) {
   constexpr int VE = ElemTraits<T>::kVec;
-  const int CV = C / VE;               // <= 128
-  const int rows = 256 / CV;           // pixel rows handled per pass by this block (>= 2)
+  const int CV = C / VE;               // <= 256 (wider layers run k_bn_bwd_reduce_wide); any value works: threads past rows * CV idle
+  const int rows = 256 / CV;           // pixel rows handled per pass by this block (>= 1)
   const int tid = threadIdx.x;
   const int cv = tid % CV, row = tid / CV;
   const bool active = row < rows;
@@ -1383,6 +1387,21 @@ using namespace vk;
     default: vkh::set_error("bad dtype %d", (int)dt); return VK_ERR_ARG; \
   }
 
+// Channel counts of the flat per-channel passes (vk_bn_add_relu, vk_bn_bwd_reduce, vk_bn_bwd_apply[_fused]): a multiple of 8 up to 512
+// (the 512-entry coefficient table) or 1024 / 2048 (the wide instances).  A count that is not a positive multiple of 8 is a bad argument;
+// a well-formed one the kernels cannot do is VK_ERR_UNSUPPORTED.  Checked before anything touches the stream.
+static int check_flat_channels(const char* fn, int C) {
+  if (C <= 0 || C % 8 != 0) {
+    vkh::set_error("%s: C=%d is not a positive multiple of 8", fn, C);
+    return VK_ERR_ARG;
+  }
+  if (C > 512 && C != 1024 && C != kWideC) {
+    vkh::set_error("%s: C=%d unsupported (a multiple of 8 up to 512, or 1024 / 2048)", fn, C);
+    return VK_ERR_UNSUPPORTED;
+  }
+  return VK_OK;
+}
+
 extern "C" int vk_input_transform(vk_dtype dtype, int N, int H, int W, const float* x, void* x4, void* stream) {
   VK_CHECK_ARG(x && x4 && N > 0 && H > 0 && W > 0, "vk_input_transform: bad argument");
   hipStream_t st = (hipStream_t)stream;
@@ -1398,6 +1417,7 @@ extern "C" int vk_bn_finalize(int C, int train, const double* stats, double coun
                               float* save_mean, float* save_invstd, void* stream) {
   VK_CHECK_ARG(C > 0 && gamma && beta && scale && shift, "vk_bn_finalize: null argument");
   VK_CHECK_ARG(train ? (stats != nullptr && count > 0) : (running_mean && running_var), "vk_bn_finalize: missing statistics");
+  VK_CHECK_ARG(!running_mean == !running_var, "vk_bn_finalize: running_mean and running_var are given together or not at all");
   vkh::ProfScope ps_("bn_finalize", (hipStream_t)stream, 0.0, (double)C * 40.0);
   hipLaunchKernelGGL(k_bn_finalize, dim3((C + 7) / 8), dim3(256), 0, (hipStream_t)stream, C, train, stats, count, gamma, beta,
                      running_mean, running_var, eps, momentum, scale, shift, save_mean, save_invstd);
@@ -1448,17 +1468,17 @@ extern "C" int vk_maxpool_bwd_bn_reduce(vk_dtype dtype, int N, int H, int W, int
 
 extern "C" int vk_bn_add_relu(vk_dtype dtype, size_t pixels, int C, const void* z, const float* scale, const float* shift,
                               const void* res, const float* rscale, const float* rshift, void* out, void* stream) {
-  VK_CHECK_ARG(z && scale && shift && res && out && C % 8 == 0, "vk_bn_add_relu: bad argument");
+  VK_CHECK_ARG(z && scale && shift && res && out, "vk_bn_add_relu: null argument");
+  if (const int rc = check_flat_channels("vk_bn_add_relu", C)) return rc;
   hipStream_t st = (hipStream_t)stream;
   vkh::ProfScope ps_("bn_add_relu", st, 0.0, (double)pixels * C * (dtype == VK_F32 ? 4.0 : 2.0) * 3.0);
-  VK_CHECK_ARG(C <= 512 || (C <= kWideC && (C & (C - 1)) == 0), "vk_bn_add_relu: C=%d unsupported", C);
-  // four vectors per thread (one unrolled pass) before the grid grows; the grid stays a multiple of C/VE threads.  Layers wider than
+  // four vectors per thread (one unrolled pass) before the grid grows; channel_grid keeps grid * 256 a multiple of C/VE threads.  Layers wider than
   // 512 channels (resnet50's block tails) run an instance with a larger coefficient table; the others keep the 512-entry one
   if (C <= 512) {
-    DISPATCH_T(dtype, hipLaunchKernelGGL((k_bn_add_relu<T, 512>), dim3(grid_for((pixels * (C / ElemTraits<T>::kVec) + 3) / 4)), dim3(256), 0, st,
-                                         pixels, C, (const T*)z, scale, shift, (const T*)res, rscale, rshift, (T*)out));
+    DISPATCH_T(dtype, hipLaunchKernelGGL((k_bn_add_relu<T, 512>), dim3(channel_grid(grid_for((pixels * (C / ElemTraits<T>::kVec) + 3) / 4), C / ElemTraits<T>::kVec)),
+                                         dim3(256), 0, st, pixels, C, (const T*)z, scale, shift, (const T*)res, rscale, rshift, (T*)out));
   } else {
-    DISPATCH_T(dtype, hipLaunchKernelGGL((k_bn_add_relu<T, kWideC>), dim3(wide_grid(grid_for((pixels * (C / ElemTraits<T>::kVec) + 3) / 4), C / ElemTraits<T>::kVec)),
+    DISPATCH_T(dtype, hipLaunchKernelGGL((k_bn_add_relu<T, kWideC>), dim3(channel_grid(grid_for((pixels * (C / ElemTraits<T>::kVec) + 3) / 4), C / ElemTraits<T>::kVec)),
                                          dim3(256), 0, st, pixels, C, (const T*)z, scale, shift, (const T*)res, rscale, rshift, (T*)out));
   }
   VK_CHECK_HIP(hipGetLastError());
@@ -1498,7 +1518,7 @@ extern "C" int vk_bn_bwd_reduce(vk_dtype dtype, size_t pixels, int C, const void
   VK_CHECK_ARG(mask_mode >= 0 && mask_mode <= 2, "vk_bn_bwd_reduce: mask_mode %d", mask_mode);
   VK_CHECK_ARG(mask_mode != 1 || (scale && shift), "vk_bn_bwd_reduce: mask_mode 1 needs scale/shift");
   VK_CHECK_ARG(mask_mode != 2 || mask_src, "vk_bn_bwd_reduce: mask_mode 2 needs mask_src");
-  VK_CHECK_ARG(C % 8 == 0 && (C <= 512 || (C <= kWideC && (C & (C - 1)) == 0)), "vk_bn_bwd_reduce: C=%d unsupported", C);
+  if (const int rc = check_flat_channels("vk_bn_bwd_reduce", C)) return rc;
   hipStream_t st = (hipStream_t)stream;
   vkh::ProfScope ps_("bn_bwd_reduce", st, 0.0, (double)pixels * C * (dtype == VK_F32 ? 4.0 : 2.0) * (mask_mode == 2 ? 3.0 : 2.0));
   DISPATCH_T(dtype, launch_bn_bwd_reduce<T>(pixels, C, dy, z, mask_mode, scale, shift, mask_src, sums, st));
@@ -1535,9 +1555,9 @@ struct BnApplyArgs {
 template <typename T>
 static int launch_bn_bwd_apply(const BnApplyArgs& a, hipStream_t st) {
   const int CV = a.C / ElemTraits<T>::kVec;
-  // grid * 256 must be a multiple of CV (<= 128 up to 512 channels: any block count works); keep enough blocks to fill the chip
+  // grid * 256 must be a multiple of CV (channel_grid: no change for a power-of-two CV up to 256); keep enough blocks to fill the chip
   const bool wide = a.C > 512;
-  dim3 grid(wide ? wide_grid(grid_for(a.pixels * CV / 2 + 1), CV) : grid_for(a.pixels * CV / 2 + 1)), block(256);
+  dim3 grid(channel_grid(grid_for(a.pixels * CV / 2 + 1), CV)), block(256);
   if (wide) {
 #define VK_APPLY_W(M) hipLaunchKernelGGL((k_bn_bwd_apply<T, M, kWideC>), grid, block, 0, st, a.pixels, a.C, (const T*)a.dy, (const T*)a.z, a.scale, \
     a.shift, (const T*)a.mask_src, a.coef, a.sums, a.count, a.gamma, a.mean, a.invstd, a.dgamma, a.dbeta, (T*)a.dz, (T*)a.g_out, a.g_acc)
@@ -1561,7 +1581,7 @@ static int bn_bwd_apply_common(vk_dtype dtype, const BnApplyArgs& a, void* strea
   VK_CHECK_ARG(a.mask_mode >= 0 && a.mask_mode <= 2, "vk_bn_bwd_apply: mask_mode %d", a.mask_mode);
   VK_CHECK_ARG(a.mask_mode != 1 || (a.scale && a.shift), "vk_bn_bwd_apply: mask_mode 1 needs scale/shift");
   VK_CHECK_ARG(a.mask_mode != 2 || a.mask_src, "vk_bn_bwd_apply: mask_mode 2 needs mask_src");
-  VK_CHECK_ARG(a.C % 8 == 0 && (a.C <= 512 || (a.C <= kWideC && (a.C & (a.C - 1)) == 0)), "vk_bn_bwd_apply: C=%d unsupported", a.C);
+  if (const int rc = check_flat_channels("vk_bn_bwd_apply", a.C)) return rc;
   hipStream_t st = (hipStream_t)stream;
   vkh::ProfScope ps_("bn_bwd_apply", st, 0.0, (double)a.pixels * a.C * (dtype == VK_F32 ? 4.0 : 2.0) * ((a.mask_mode == 2 ? 4.0 : 3.0) + (a.g_out ? (a.g_acc ? 2.0 : 1.0) : 0.0)));
   DISPATCH_T(dtype, launch_bn_bwd_apply<T>(a, st));

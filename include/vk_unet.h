@@ -470,6 +470,55 @@ int vk_multilabel_loss(int N, int C, int HW, const float* logits, const float* t
 int vk_multiclass_loss(int N, int C, int HW, const float* logits, const int64_t* target, void* workspace, size_t workspace_bytes,
                        float* loss_out, float* dlogits, float grad_scale, float w_ce, float w_dice, void* stream);
 
+/* ---- configurable loss (seg_loss.hip): a weighted sum of at most one term of each kind, in one reduction pass, one single-workgroup
+ * finalize and one backward pass whatever the number of terms.  x fp32 [N][C][HW], 1 <= C <= 16; mode VK_LOSS_BINARY (C == 1) and
+ * VK_LOSS_MULTILABEL: target fp32 [N][C][HW], p = sigmoid of x; VK_LOSS_MULTICLASS (C >= 2): target int64 [N][HW], p = softmax over c.
+ * m = validity mask (target != ignore_index when has_ignore; multiclass: per pixel), y = target (multiclass: one-hot), both masked.
+ *   pix      BCE-with-logits on the soft target (1 - y) sf + y (1 - sf) with pos_weight as torch (sigmoid modes), or cross-entropy
+ *            (1 - sf) nll + (sf / C) sum_c -log p_c (multiclass); ignored entries add 0; divided by ALL entries (pix_denom_valid = 0:
+ *            smp SoftBCEWithLogitsLoss / SoftCrossEntropyLoss) or by the VALID ones (1: torch.nn)
+ *   focal    b = BCE-with-logits of x against y; (1 - e^-b)^gamma b (alpha y + (1 - alpha)(1 - y) when focal_has_alpha), mean over the
+ *            valid entries; multiclass: the sum over c of that loss on plane c against [t == c].  gamma is 0 or >= 1.
+ *   dice     s = (2 I + smooth) / max(P + T + smooth, eps)                  I = sum p y, P = sum p, T = sum y over (N, HW) per class
+ *   jaccard  s = (I + smooth) / max(P + T - I + smooth, eps)
+ *   tversky  s = (I + smooth) / max(I + alpha (P - I) + beta (T - I) + smooth, eps); the class mean is raised to tversky_gamma >= 1
+ *            each: l_c = -log max(s, eps) when *_log else 1 - s; l_c = 0 where T_c = 0; mean over the classes of *_classes (bit c =
+ *            class c; 0 = all C)
+ * A term whose denominator is zero because every entry is ignored is 0.  terms: bit 0 pix, 1 focal, 2 dice, 3 jaccard, 4 tversky.
+ * struct_size must be the size of the structure (versioning). */
+typedef struct vk_seg_loss_cfg {
+  uint32_t struct_size;
+  int32_t mode;
+  uint32_t terms;
+  int32_t has_ignore, ignore_index;
+  float w_pix, w_focal, w_dice, w_jaccard, w_tversky;
+  float pix_smooth;
+  int32_t pix_denom_valid, has_pos_weight;
+  float pos_weight[16];
+  int32_t focal_has_alpha;
+  float focal_alpha, focal_gamma;
+  float dice_smooth, dice_eps;
+  int32_t dice_log;
+  uint32_t dice_classes;
+  float jaccard_smooth, jaccard_eps;
+  int32_t jaccard_log;
+  uint32_t jaccard_classes;
+  float tversky_smooth, tversky_eps;
+  int32_t tversky_log;
+  uint32_t tversky_classes;
+  float tversky_alpha, tversky_beta, tversky_gamma;
+} vk_seg_loss_cfg;
+size_t vk_seg_loss_cfg_size(void);
+/* Device scratch for logits [N][C][HW] in any mode (8-byte aligned). */
+size_t vk_seg_loss_workspace_bytes(int N, int C, int HW);
+/* loss_out float[8] = {total, pix, focal, dice, jaccard, tversky, bad labels, 0} (absent terms 0); dlogits (optional) = grad_scale *
+ * d total / dx, exactly 0 at ignored entries.  A multiclass label that is neither in [0, C) nor ignore_index is an argument error
+ * reported on the device as in vk_multiclass_loss: values NaN, loss_out[6] = their number, zero gradient there, nothing faults.
+ * The configuration is checked on the host first (VK_ERR_ARG and vk_last_error_string).  Per-workgroup fp64 partial rows added in a
+ * fixed order: the same inputs give the same bits.  16-byte accesses when HW % 4 == 0 and the buffers are 16-byte aligned. */
+int vk_seg_loss(const vk_seg_loss_cfg* cfg, int N, int C, int HW, const float* logits, const void* target, void* workspace,
+                size_t workspace_bytes, float* loss_out, float* dlogits, float grad_scale, void* stream);
+
 /* Thresholded Dice / IoU of the reference's validate() (train.py:230-255 `dice_coef`, :259-281 `iou_coef`, :518-522):
  * per image i of `per_image` elements, pred = (p > threshold) as 0/1, I = sum pred*t, P = sum pred, T = sum t;
  * dice_i = (2 I + eps) / (P + T + eps), iou_i = (I + eps) / (P + T - I + eps) in fp32.
@@ -608,6 +657,10 @@ int vk_unet_loss(vk_unet* h, const float* logits, const float* target, float* lo
 #define VK_LOSS_MULTICLASS 2
 int vk_unet_loss_ex(vk_unet* h, int mode, const void* logits, const void* target, float* loss_out, float grad_scale, float w_ce,
                     float w_dice, void* stream);
+/* Loss of any plan from a configuration structure as vk_seg_loss takes it: C = the plan's classes, target per cfg->mode, loss_out float[8].  A
+ * training plan's dlogits are left in the workspace for vk_unet_backward, as the two calls above do. */
+int vk_unet_loss_cfg(vk_unet* h, const vk_seg_loss_cfg* cfg, const void* logits, const void* target, float* loss_out,
+                     float grad_scale, void* stream);
 /* dlogits: fp32 [N][C][S][S] gradient of the loss wrt the logits, or NULL to use the one vk_unet_loss
  * left in the workspace.  Runs backward stages [stage_begin, stage_end); stage i completes gradient bucket i.  Gradients are
  * accumulated into the flat grad buffer (caller zeroes it once per step, e.g. via vk_unet_zero_grad).

@@ -66,6 +66,18 @@ class vk_aug_params(C.Structure):
                 ("noise_seed", C.c_uint32), ("clahe_limit", C.c_int)]
 
 
+class vk_seg_loss_cfg(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("terms", C.c_uint32), ("has_ignore", C.c_int32),
+                ("ignore_index", C.c_int32), ("w_pix", C.c_float), ("w_focal", C.c_float), ("w_dice", C.c_float),
+                ("w_jaccard", C.c_float), ("w_tversky", C.c_float), ("pix_smooth", C.c_float), ("pix_denom_valid", C.c_int32),
+                ("has_pos_weight", C.c_int32), ("pos_weight", C.c_float * 16), ("focal_has_alpha", C.c_int32),
+                ("focal_alpha", C.c_float), ("focal_gamma", C.c_float),
+                ("dice_smooth", C.c_float), ("dice_eps", C.c_float), ("dice_log", C.c_int32), ("dice_classes", C.c_uint32),
+                ("jaccard_smooth", C.c_float), ("jaccard_eps", C.c_float), ("jaccard_log", C.c_int32), ("jaccard_classes", C.c_uint32),
+                ("tversky_smooth", C.c_float), ("tversky_eps", C.c_float), ("tversky_log", C.c_int32), ("tversky_classes", C.c_uint32),
+                ("tversky_alpha", C.c_float), ("tversky_beta", C.c_float), ("tversky_gamma", C.c_float)]
+
+
 class vk_unet_config(C.Structure):
     _fields_ = [("N", C.c_int), ("size", C.c_int), ("dtype", C.c_int), ("training", C.c_int), ("width", C.c_int)]
 
@@ -141,6 +153,9 @@ SIGNATURES = {
     "vk_multi_loss_workspace_bytes": (sz, [ci, ci, ci]),
     "vk_multilabel_loss": (ci, [ci, ci, ci, vp, vp, vp, sz, vp, vp, cf, cf, cf, vp]),
     "vk_multiclass_loss": (ci, [ci, ci, ci, vp, vp, vp, sz, vp, vp, cf, cf, cf, vp]),
+    "vk_seg_loss_cfg_size": (sz, []),
+    "vk_seg_loss_workspace_bytes": (sz, [ci, ci, ci]),
+    "vk_seg_loss": (ci, [P(vk_seg_loss_cfg), ci, ci, ci, vp, vp, vp, sz, vp, vp, cf, vp]),
     "vk_seg_metrics_workspace_bytes": (C.c_size_t, [ci]),
     "vk_seg_metrics": (ci, [ci, sz, vp, vp, ci, cf, cf, vp, sz, vp, vp]),
     "vk_seg_metrics_multi_workspace_bytes": (sz, [ci, ci]),
@@ -170,6 +185,7 @@ SIGNATURES = {
     "vk_unet_forward": (ci, [vp, vp, vp, ci, vp]),
     "vk_unet_loss": (ci, [vp, vp, vp, vp, cf, cf, cf, vp]),
     "vk_unet_loss_ex": (ci, [vp, ci, vp, vp, vp, cf, cf, cf, vp]),
+    "vk_unet_loss_cfg": (ci, [vp, P(vk_seg_loss_cfg), vp, vp, vp, cf, vp]),
     "vk_unet_backward": (ci, [vp, vp, ci, ci, vp]),
     "vk_unet_set_trainable": (ci, [vp, P(C.c_uint8), ci]),
     "vk_unet_set_bn_frozen": (ci, [vp, P(C.c_uint8), ci]),

@@ -495,6 +495,7 @@ struct vk_unet {
   std::vector<CastRange> cast_tab;
   size_t off_tab_cast = 0;
   size_t off_gscratch = 0;          // sink of the gamma / beta / head gradients of frozen tensors (never read)
+  size_t off_sloss = 0, sloss_bytes = 0;   // every plan: scratch of vk_seg_loss (vk_unet_loss_cfg), the last region of the workspace
   size_t off_mloss = 0, mloss_bytes = 0;   // classes > 1: partial sums of vk_multilabel_loss / vk_multiclass_loss
   std::vector<BnEvalEntry> bn_tab;
   std::map<std::string, std::pair<void*, std::vector<int>>> debug;
@@ -801,6 +802,8 @@ void layout_workspace(vk_unet* h) {
     h->mloss_bytes = vk_multi_loss_workspace_bytes(N, h->classes, S * SW);
     h->off_mloss = take(h->mloss_bytes);
   }
+  h->sloss_bytes = vk_seg_loss_workspace_bytes(N, h->classes, S * SW);      // behind everything: no earlier offset moves
+  h->off_sloss = take(h->sloss_bytes);
   h->ws_bytes = off;
 }
 
@@ -1298,6 +1301,14 @@ extern "C" int vk_unet_loss_ex(vk_unet* h, int mode, const void* logits, const v
                               dl, grad_scale, w_ce, w_dice, stream);
   return vk_multiclass_loss(N, h->classes, HW, (const float*)logits, (const int64_t*)target, h->ws + h->off_mloss, h->mloss_bytes, loss_out,
                             dl, grad_scale, w_ce, w_dice, stream);
+}
+
+extern "C" int vk_unet_loss_cfg(vk_unet* h, const vk_seg_loss_cfg* cfg, const void* logits, const void* target, float* loss_out,
+                                float grad_scale, void* stream) {
+  VK_CHECK_ARG(h && h->bound && cfg && logits && target && loss_out, "vk_unet_loss_cfg: plan not bound or null argument");
+  float* dl = h->cfg.training ? (float*)(h->ws + h->off_dlogits) : nullptr;
+  return vk_seg_loss(cfg, h->cfg.N, h->classes, h->cfg.size * h->cfg.width, (const float*)logits, target, h->ws + h->off_sloss,
+                     h->sloss_bytes, loss_out, dl, grad_scale, stream);
 }
 
 extern "C" int vk_unet_loss(vk_unet* h, const float* logits, const float* target, float* loss_out, float grad_scale, float w_bce,

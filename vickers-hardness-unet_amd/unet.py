@@ -501,7 +501,7 @@ class Unet(nn.Module):
 
     # ------------------------------------------------------------------ fused step (no autograd graph)
     def loss_and_backward(self, x: torch.Tensor, y: torch.Tensor, grad_scale: float = 1.0,
-                          dtype: Optional[torch.dtype] = None, mode: Optional[str] = None) -> torch.Tensor:
+                          dtype: Optional[torch.dtype] = None, mode: Optional[str] = None, loss=None) -> torch.Tensor:
         """forward (BatchNorm layers in their modules' modes) + loss + backward in one call; the engine's loss kernel feeds the
         head gradient directly.  Returns a device tensor [total, bce or ce, dice] (no host sync).
         Equivalent to train.py:436-448 ``logits = model(x); loss = bce + dice; loss.backward()``; ``requires_grad`` of the parameters
@@ -509,7 +509,13 @@ class Unet(nn.Module):
         ``mode``: None / "binary" (classes == 1: BCEWithLogitsLoss + DiceLoss("binary")), "multilabel" (y fp32 [N,C,H,W]:
         BCEWithLogitsLoss + DiceLoss("multilabel")) or "multiclass" (y int64 [N,H,W] in [0, C): CrossEntropyLoss +
         DiceLoss("multiclass"); a label outside [0, C) makes the result NaN).  With classes > 1 the mode must be
-        given."""
+        given.
+        ``loss``: a ``vk.seglosses`` term or sum instead of ``mode`` (the two exclude each other): the same step with that loss
+        (vk_unet_loss_cfg); returns a device tensor [total, pix, focal, dice, jaccard, tversky] of a buffer of its own."""
+        if loss is not None:
+            if mode is not None:
+                raise ValueError("loss_and_backward: give mode= or loss=, not both")
+            return self._loss_cfg_and_backward(x, y, grad_scale, dtype, loss)
         if mode is None:
             if self.classes != 1:
                 raise ValueError("loss_and_backward: classes=%d needs mode='multilabel' or mode='multiclass'" % self.classes)
@@ -541,6 +547,35 @@ class Unet(nn.Module):
         self._run_backward(plan, None, mask)
         self.last_logits = logits
         return plan.loss_out[:3]
+
+
+    def _loss_cfg_and_backward(self, x, y, grad_scale, dtype, loss) -> torch.Tensor:
+        from . import seglosses
+        S = seglosses.as_loss_sum(loss)
+        self._check_input(x)
+        mask = self._trainable_mask()
+        if not any(mask):
+            raise VkError("loss_and_backward: no parameter requires grad (every tensor is frozen)")
+        N, _, H, W = x.shape
+        cfg = S.cfg(self.classes)
+        multiclass = cfg.mode == _lib.VK_LOSS_MULTICLASS
+        if multiclass:
+            if tuple(y.shape) != (N, H, W) or y.dtype != torch.int64:
+                raise ValueError("loss_and_backward(loss=<multiclass>): target must be int64 [N,H,W], got %s %s" % (y.dtype, tuple(y.shape)))
+        elif y.dim() != 4 or y.shape[0] != N or y.shape[1] not in (1, self.classes) or tuple(y.shape[2:]) != (H, W):
+            raise ValueError("loss_and_backward(loss=...): target must be [N,%d,H,W], got %s" % (self.classes, tuple(y.shape)))
+        plan = self.plan_for(N, H if H == W else (H, W), dtype or self.compute_dtype, True)
+        logits = self._run_forward(plan, x, True)
+        y = y.detach().contiguous() if multiclass else y.detach().float().expand(N, self.classes, H, W).contiguous()
+        out = getattr(plan, "seg_loss_out", None)
+        if out is None:
+            out = plan.seg_loss_out = torch.zeros(8, dtype=torch.float32, device=logits.device)
+        check(lib().vk_unet_loss_cfg(plan.h, cfg, logits.data_ptr(), y.data_ptr(), out.data_ptr(), float(grad_scale),
+                                     _lib.current_stream()), "vk_unet_loss_cfg")
+        self._run_backward(plan, None, mask)
+        self.last_logits = logits
+        S.last_components = out[:6]
+        return out[:6]
 
 
 def build_model(encoder: str = "resnet34", weights: Optional[str] = "imagenet") -> Unet:

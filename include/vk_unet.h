@@ -484,7 +484,10 @@ int vk_multiclass_loss(int N, int C, int HW, const float* logits, const int64_t*
  *   tversky  s = (I + smooth) / max(I + alpha (P - I) + beta (T - I) + smooth, eps); the class mean is raised to tversky_gamma >= 1
  *            each: l_c = -log max(s, eps) when *_log else 1 - s; l_c = 0 where T_c = 0; mean over the classes of *_classes (bit c =
  *            class c; 0 = all C)
- * A term whose denominator is zero because every entry is ignored is 0.  terms: bit 0 pix, 1 focal, 2 dice, 3 jaccard, 4 tversky.
+ *   mcc      (mode VK_LOSS_BINARY only) tp = I + eps, fp = P - I + eps, fn = T - I + eps, tn = M - P - T + I + eps, M = valid entries;
+ *            1 - (tp tn - fp fn) / sqrt((tp + fp)(tp + fn)(tn + fp)(tn + fn)), eps = mcc_eps > 0
+ * A term whose denominator is zero because every entry is ignored is 0.  terms: bit 0 pix, 1 focal, 2 dice, 3 jaccard, 4 tversky,
+ * 5 mcc.
  * struct_size must be the size of the structure (versioning). */
 typedef struct vk_seg_loss_cfg {
   uint32_t struct_size;
@@ -507,17 +510,48 @@ typedef struct vk_seg_loss_cfg {
   int32_t tversky_log;
   uint32_t tversky_classes;
   float tversky_alpha, tversky_beta, tversky_gamma;
+  float w_mcc, mcc_eps;    /* appended: no earlier field moved */
 } vk_seg_loss_cfg;
 size_t vk_seg_loss_cfg_size(void);
 /* Device scratch for logits [N][C][HW] in any mode (8-byte aligned). */
 size_t vk_seg_loss_workspace_bytes(int N, int C, int HW);
-/* loss_out float[8] = {total, pix, focal, dice, jaccard, tversky, bad labels, 0} (absent terms 0); dlogits (optional) = grad_scale *
+/* loss_out float[8] = {total, pix, focal, dice, jaccard, tversky, bad labels, mcc} (absent terms 0); dlogits (optional) = grad_scale *
  * d total / dx, exactly 0 at ignored entries.  A multiclass label that is neither in [0, C) nor ignore_index is an argument error
  * reported on the device as in vk_multiclass_loss: values NaN, loss_out[6] = their number, zero gradient there, nothing faults.
  * The configuration is checked on the host first (VK_ERR_ARG and vk_last_error_string).  Per-workgroup fp64 partial rows added in a
  * fixed order: the same inputs give the same bits.  16-byte accesses when HW % 4 == 0 and the buffers are 16-byte aligned. */
 int vk_seg_loss(const vk_seg_loss_cfg* cfg, int N, int C, int HW, const float* logits, const void* target, void* workspace,
                 size_t workspace_bytes, float* loss_out, float* dlogits, float grad_scale, void* stream);
+
+/* ---- Lovasz losses (lovasz.hip): a stable device radix sort of the errors (descending, equal errors by ascending flat index; errors
+ * compare as fp32 bit patterns in radix order), an integer prefix count of the labels over that order, the Jaccard increments dJ in
+ * closed form and a scatter of the gradient back.  logits fp32 [N][C][HW], 1 <= C <= 16, targets as vk_seg_loss takes them.
+ *   VK_LOSS_BINARY / VK_LOSS_MULTILABEL (hinge): e = 1 - x (2 y - 1); entries with y == ignore_index are left out; a segment is the
+ *     whole batch or (per_image) one image's C HW entries; segment loss = sum_k relu(e_(k)) dJ_k; the result is the mean over the
+ *     segments (a segment without a valid entry is 0).
+ *   VK_LOSS_MULTICLASS (softmax): p = softmax over c; per class c present among the valid labels of the segment: e = |[t == c] - p_c|,
+ *     class loss = sum_k e_(k) dJ_k; segment loss = mean over the present classes; mean over the segments.  A label that is neither a
+ *     class nor ignore_index is counted (loss_out[1]), never used as an index, and makes the value NaN.
+ * struct_size must be the size of the structure. */
+typedef struct vk_lovasz_cfg {
+  uint32_t struct_size;
+  int32_t mode, per_image, has_ignore, ignore_index;
+} vk_lovasz_cfg;
+size_t vk_lovasz_cfg_size(void);
+/* Device scratch of vk_lovasz_loss (8-byte aligned; the caller owns it, it is no part of a plan's workspace); 0 for a configuration or
+ * shape the call would refuse (more than 2^31 - 1 entries among them). */
+size_t vk_lovasz_workspace_bytes(const vk_lovasz_cfg* cfg, int N, int C, int HW);
+/* loss_out float[4] = {value, bad labels, 0, 0}; dlogits (optional) = grad_scale * d value / dx, written (accumulate = 0: exactly 0 at
+ * ignored entries and where the error is not positive) or added (accumulate = 1: ignored entries are left unchanged).  The same inputs
+ * give the same bits.  NaN or infinite logits give meaningless values, never an access outside the buffers. */
+int vk_lovasz_loss(const vk_lovasz_cfg* cfg, int N, int C, int HW, const float* logits, const void* target, void* workspace,
+                   size_t workspace_bytes, float* loss_out, float* dlogits, float grad_scale, int accumulate, void* stream);
+/* The sort / scan / apply core on caller-supplied errors fp32 [S][L] with flag uint8 [S][L] (0 background, 1 foreground, 2 ignored):
+ * loss_out float[S] = sum_k relu(e_(k)) dJ_k per segment; derr_out (optional) fp32 [S][L] = dJ at the entry's rank where e > 0, else 0;
+ * rank_out (optional) uint32 [S][L] = the entry's position in the sorted order of its segment, 0xFFFFFFFF for ignored entries. */
+size_t vk_lovasz_flat_workspace_bytes(int S, int64_t L);
+int vk_lovasz_flat(const float* errors, const uint8_t* flag, int S, int64_t L, void* workspace, size_t workspace_bytes, float* loss_out,
+                   float* derr_out, uint32_t* rank_out, void* stream);
 
 /* Thresholded Dice / IoU of the reference's validate() (train.py:230-255 `dice_coef`, :259-281 `iou_coef`, :518-522):
  * per image i of `per_image` elements, pred = (p > threshold) as 0/1, I = sum pred*t, P = sum pred, T = sum t;
@@ -661,6 +695,12 @@ int vk_unet_loss_ex(vk_unet* h, int mode, const void* logits, const void* target
  * training plan's dlogits are left in the workspace for vk_unet_backward, as the two calls above do. */
 int vk_unet_loss_cfg(vk_unet* h, const vk_seg_loss_cfg* cfg, const void* logits, const void* target, float* loss_out,
                      float grad_scale, void* stream);
+/* The fused step with a Lovasz term: runs vk_seg_loss on seg_cfg as vk_unet_loss_cfg does (seg_cfg may be NULL: no such part), then
+ * adds w_lovasz times the Lovasz gradient into the plan's dlogits and w_lovasz times its value into the total.  workspace: of
+ * vk_lovasz_workspace_bytes(lovasz_cfg, N, classes, S S), the caller's.  loss_out float[16]: [0, 8) as vk_seg_loss (total and bad
+ * labels include the Lovasz part), [8] the Lovasz value, [9] its bad labels. */
+int vk_unet_loss_lovasz(vk_unet* h, const vk_seg_loss_cfg* seg_cfg, const vk_lovasz_cfg* lovasz_cfg, float w_lovasz, const void* logits,
+                        const void* target, void* workspace, size_t workspace_bytes, float* loss_out, float grad_scale, void* stream);
 /* dlogits: fp32 [N][C][S][S] gradient of the loss wrt the logits, or NULL to use the one vk_unet_loss
  * left in the workspace.  Runs backward stages [stage_begin, stage_end); stage i completes gradient bucket i.  Gradients are
  * accumulated into the flat grad buffer (caller zeroes it once per step, e.g. via vk_unet_zero_grad).

@@ -75,7 +75,13 @@ class vk_seg_loss_cfg(C.Structure):
                 ("dice_smooth", C.c_float), ("dice_eps", C.c_float), ("dice_log", C.c_int32), ("dice_classes", C.c_uint32),
                 ("jaccard_smooth", C.c_float), ("jaccard_eps", C.c_float), ("jaccard_log", C.c_int32), ("jaccard_classes", C.c_uint32),
                 ("tversky_smooth", C.c_float), ("tversky_eps", C.c_float), ("tversky_log", C.c_int32), ("tversky_classes", C.c_uint32),
-                ("tversky_alpha", C.c_float), ("tversky_beta", C.c_float), ("tversky_gamma", C.c_float)]
+                ("tversky_alpha", C.c_float), ("tversky_beta", C.c_float), ("tversky_gamma", C.c_float),
+                ("w_mcc", C.c_float), ("mcc_eps", C.c_float)]
+
+
+class vk_lovasz_cfg(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("per_image", C.c_int32), ("has_ignore", C.c_int32),
+                ("ignore_index", C.c_int32)]
 
 
 class vk_unet_config(C.Structure):
@@ -156,6 +162,11 @@ SIGNATURES = {
     "vk_seg_loss_cfg_size": (sz, []),
     "vk_seg_loss_workspace_bytes": (sz, [ci, ci, ci]),
     "vk_seg_loss": (ci, [P(vk_seg_loss_cfg), ci, ci, ci, vp, vp, vp, sz, vp, vp, cf, vp]),
+    "vk_lovasz_cfg_size": (sz, []),
+    "vk_lovasz_workspace_bytes": (sz, [P(vk_lovasz_cfg), ci, ci, ci]),
+    "vk_lovasz_loss": (ci, [P(vk_lovasz_cfg), ci, ci, ci, vp, vp, vp, sz, vp, vp, cf, ci, vp]),
+    "vk_lovasz_flat_workspace_bytes": (sz, [ci, i64]),
+    "vk_lovasz_flat": (ci, [vp, vp, ci, i64, vp, sz, vp, vp, vp, vp]),
     "vk_seg_metrics_workspace_bytes": (C.c_size_t, [ci]),
     "vk_seg_metrics": (ci, [ci, sz, vp, vp, ci, cf, cf, vp, sz, vp, vp]),
     "vk_seg_metrics_multi_workspace_bytes": (sz, [ci, ci]),
@@ -186,6 +197,7 @@ SIGNATURES = {
     "vk_unet_loss": (ci, [vp, vp, vp, vp, cf, cf, cf, vp]),
     "vk_unet_loss_ex": (ci, [vp, ci, vp, vp, vp, cf, cf, cf, vp]),
     "vk_unet_loss_cfg": (ci, [vp, P(vk_seg_loss_cfg), vp, vp, vp, cf, vp]),
+    "vk_unet_loss_lovasz": (ci, [vp, P(vk_seg_loss_cfg), P(vk_lovasz_cfg), cf, vp, vp, vp, sz, vp, cf, vp]),
     "vk_unet_backward": (ci, [vp, vp, ci, ci, vp]),
     "vk_unet_set_trainable": (ci, [vp, P(C.c_uint8), ci]),
     "vk_unet_set_bn_frozen": (ci, [vp, P(C.c_uint8), ci]),

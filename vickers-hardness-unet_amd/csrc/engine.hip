@@ -1311,6 +1311,24 @@ extern "C" int vk_unet_loss_cfg(vk_unet* h, const vk_seg_loss_cfg* cfg, const vo
                      h->sloss_bytes, loss_out, dl, grad_scale, stream);
 }
 
+extern "C" int vk_unet_loss_lovasz(vk_unet* h, const vk_seg_loss_cfg* seg_cfg, const vk_lovasz_cfg* lovasz_cfg, float w_lovasz,
+                                   const void* logits, const void* target, void* workspace, size_t workspace_bytes, float* loss_out,
+                                   float grad_scale, void* stream) {
+  VK_CHECK_ARG(h && h->bound && lovasz_cfg && logits && target && workspace && loss_out,
+               "vk_unet_loss_lovasz: plan not bound or null argument");
+  VK_CHECK_ARG(w_lovasz == w_lovasz && w_lovasz - w_lovasz == 0.f, "vk_unet_loss_lovasz: w_lovasz is not finite");
+  VK_CHECK_ARG(!seg_cfg || seg_cfg->mode == lovasz_cfg->mode, "vk_unet_loss_lovasz: the two parts disagree on the mode");
+  const int N = h->cfg.N, HW = h->cfg.size * h->cfg.width;
+  float* dl = h->cfg.training ? (float*)(h->ws + h->off_dlogits) : nullptr;
+  hipStream_t st = (hipStream_t)stream;
+  if (seg_cfg) RET_IF(vk_seg_loss(seg_cfg, N, h->classes, HW, (const float*)logits, target, h->ws + h->off_sloss, h->sloss_bytes, loss_out,
+                                  dl, grad_scale, stream));
+  else VK_CHECK_HIP(hipMemsetAsync(loss_out, 0, 8 * sizeof(float), st));
+  RET_IF(vk_lovasz_loss(lovasz_cfg, N, h->classes, HW, (const float*)logits, target, workspace, workspace_bytes, loss_out + 8, dl,
+                        grad_scale * w_lovasz, seg_cfg ? 1 : 0, stream));
+  return vk::lovasz_combine(loss_out, w_lovasz, st);
+}
+
 extern "C" int vk_unet_loss(vk_unet* h, const float* logits, const float* target, float* loss_out, float grad_scale, float w_bce,
                             float w_dice, void* stream) {
   VK_CHECK_ARG(h && h->bound && logits && target && loss_out, "vk_unet_loss: plan not bound or null tensor");

@@ -2,6 +2,7 @@
 //   pix      BCE-with-logits (binary, multilabel) or cross-entropy (multiclass): label smoothing, pos_weight, mean over all / valid
 //   focal    smp focal_loss_with_logits (per class plane against [t == c] in multiclass mode)
 //   dice, jaccard, tversky   region scores from the per-class sums I = sum p y, P = sum p, T = sum y over (N, HW)
+//   mcc      (binary) Matthews correlation from the same sums and the valid count: no pass of its own
 // with one ignore_index for the whole sum, over logits fp32 [N][C][HW] (class planes), 1 <= C <= 16.  p = sigmoid(x) (binary,
 // multilabel: target fp32 [N][C][HW]) or softmax over the classes (multiclass: target int64 [N][HW]).
 // Three launches whatever the number of terms:
@@ -19,7 +20,7 @@ namespace vk {
 
 constexpr int kSlMaxC = 16;
 constexpr int kSlCoef = 64;          // doubles: [0,16) a_c, [16,32) b_c, [32] pixel-term scale, [33] focal scale, [34] bad labels
-constexpr unsigned kSlPix = 1u, kSlFocal = 2u, kSlDice = 4u, kSlJaccard = 8u, kSlTversky = 16u;
+constexpr unsigned kSlPix = 1u, kSlFocal = 2u, kSlDice = 4u, kSlJaccard = 8u, kSlTversky = 16u, kSlMcc = 32u;
 
 // what the two passes over the pixels need of the configuration
 struct SlParams {
@@ -425,6 +426,19 @@ __global__ __launch_bounds__(1024) void k_sl_finalize(vk_seg_loss_cfg cfg, int N
       coef[kSlMaxC + c] += dls * (-nd2 * dP);            // constant in y
     }
   }
+  // mcc (binary, C == 1): tp = I + eps, fp = P - I + eps, fn = T - I + eps, tn = M - P - T + I + eps.  The four factors under the
+  // root are A = P + 2 eps, B = T + 2 eps, Cn = M - T + 2 eps, D = M - P + 2 eps: none depends on I, and d num / dI = M + 4 eps,
+  // d num / dP = -B, so d loss / dp = m (a y + b) with a = -(M + 4 eps) / den, b = B / den + (num / den) (1 / A - 1 / D) / 2.
+  double v_mcc = 0.0;
+  if ((terms & kSlMcc) && valid > 0.0) {
+    const double e = cfg.mcc_eps, I = SL_I(0), P = SL_P(0), T = SL_T(0), M = valid;
+    const double tp = I + e, fp = P - I + e, fn = T - I + e, tn = M - P - T + I + e;
+    const double A = tp + fp, B = tp + fn, Cn = tn + fp, D = tn + fn;
+    const double num = tp * tn - fp * fn, den = sqrt(A * B * Cn * D);
+    v_mcc = 1.0 - num / den;
+    coef[0] += cfg.w_mcc * (-(M + 4.0 * e) / den);
+    coef[kSlMaxC] += cfg.w_mcc * (B / den + 0.5 * (num / den) * (1.0 / A - 1.0 / D));
+  }
 #undef SL_I
 #undef SL_P
 #undef SL_T
@@ -433,7 +447,7 @@ __global__ __launch_bounds__(1024) void k_sl_finalize(vk_seg_loss_cfg cfg, int N
   coef[34] = bad;
   const double total = (terms & kSlPix ? cfg.w_pix * v_pix : 0.0) + (terms & kSlFocal ? cfg.w_focal * v_foc : 0.0) +
                        (terms & kSlDice ? cfg.w_dice * v_dice : 0.0) + (terms & kSlJaccard ? cfg.w_jaccard * v_jac : 0.0) +
-                       (terms & kSlTversky ? cfg.w_tversky * v_tv : 0.0);
+                       (terms & kSlTversky ? cfg.w_tversky * v_tv : 0.0) + (terms & kSlMcc ? cfg.w_mcc * v_mcc : 0.0);
   const float nan = __builtin_nanf("");
   const bool isbad = bad > 0.0;
   loss_out[0] = isbad ? nan : (float)total;
@@ -443,7 +457,7 @@ __global__ __launch_bounds__(1024) void k_sl_finalize(vk_seg_loss_cfg cfg, int N
   loss_out[4] = isbad ? nan : (float)v_jac;
   loss_out[5] = isbad ? nan : (float)v_tv;
   loss_out[6] = (float)bad;
-  loss_out[7] = 0.f;
+  loss_out[7] = (float)v_mcc;          // binary only: never beside bad labels; 0 without the term
 }
 
 }  // namespace vk
@@ -482,7 +496,7 @@ bool sl_check_cfg(const vk_seg_loss_cfg* c, int C, const char* who) {
   SL_REQ(c->mode == VK_LOSS_BINARY || c->mode == VK_LOSS_MULTILABEL || c->mode == VK_LOSS_MULTICLASS, "%s: bad mode %d", who, c->mode);
   SL_REQ(c->mode != VK_LOSS_BINARY || C == 1, "%s: mode binary needs C == 1 (got %d)", who, C);
   SL_REQ(c->mode != VK_LOSS_MULTICLASS || C >= 2, "%s: mode multiclass needs C >= 2 (got %d)", who, C);
-  SL_REQ(c->terms != 0 && (c->terms & ~31u) == 0, "%s: terms 0x%x: at least one of the five kinds, no other bit", who, c->terms);
+  SL_REQ(c->terms != 0 && (c->terms & ~63u) == 0, "%s: terms 0x%x: at least one of the six kinds, no other bit", who, c->terms);
   SL_REQ(finite_f(c->w_pix) && finite_f(c->w_focal) && finite_f(c->w_dice) && finite_f(c->w_jaccard) && finite_f(c->w_tversky),
          "%s: a term weight is not finite", who);
   if (c->terms & kSlPix) {
@@ -506,6 +520,11 @@ bool sl_check_cfg(const vk_seg_loss_cfg* c, int C, const char* who) {
     SL_REQ(finite_f(smooth) && smooth >= 0.f, "%s: %s smooth %g must be finite and >= 0", who, nm, (double)smooth);
     SL_REQ(finite_f(eps) && eps > 0.f, "%s: %s eps %g must be > 0", who, nm, (double)eps);
     SL_REQ((cm >> C) == 0, "%s: %s classes mask 0x%x names a class >= C = %d", who, nm, cm, C);
+  }
+  if (c->terms & kSlMcc) {
+    SL_REQ(c->mode == VK_LOSS_BINARY, "%s: the mcc term needs mode binary", who);
+    SL_REQ(finite_f(c->w_mcc), "%s: a term weight is not finite", who);
+    SL_REQ(finite_f(c->mcc_eps) && c->mcc_eps > 0.f, "%s: mcc eps %g must be > 0", who, (double)c->mcc_eps);
   }
   if (c->terms & kSlTversky) {
     SL_REQ(finite_f(c->tversky_alpha) && finite_f(c->tversky_beta), "%s: tversky alpha / beta not finite", who);

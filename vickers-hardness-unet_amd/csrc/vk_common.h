@@ -344,4 +344,6 @@ bool wgrad_batch_supports(const vk_conv_desc* d);
 int wgrad_batch_build(const vk_conv_desc* descs, const void* const* dz, float* const* dw, int n, int target_blocks, void* tables,
                       size_t tables_bytes, WgradBatchPlan* plan);
 int wgrad_batch_launch(vk_dtype dt, const WgradBatchPlan& plan, const void* tables, void* slab, size_t slab_bytes, hipStream_t st);
+// lovasz.hip (used by engine.hip): loss_out[0] += w * loss_out[8], loss_out[6] += loss_out[9]
+int lovasz_combine(float* loss_out, float w, hipStream_t st);
 }  // namespace vk

@@ -1,4 +1,4 @@
-"""``smp.losses`` (minus Lovasz and MCC) on one fused, deterministic device reduction: csrc/seg_loss.hip behind ``vk_seg_loss``.
+"""``smp.losses`` (minus Lovasz and MCC, which live in ``vk.lovasz``) on one fused, deterministic device reduction: csrc/seg_loss.hip behind ``vk_seg_loss``.
 
 Constructor signatures are smp's (and torch.nn's for the last two), so a training script changes only the import::
 
@@ -36,7 +36,7 @@ __all__ = ["DiceLoss", "JaccardLoss", "TverskyLoss", "FocalLoss", "SoftBCEWithLo
            "BCEWithLogitsLoss", "LovaszLoss", "MCCLoss", "LossSum", "seg_metrics"]
 
 MODES = ("binary", "multilabel", "multiclass")
-KINDS = ("pix", "focal", "dice", "jaccard", "tversky")
+KINDS = ("pix", "focal", "dice", "jaccard", "tversky", "mcc")          # bit i of vk_seg_loss_cfg.terms; "mcc": vk.lovasz.MCCLoss
 _MODE_CODE = {"binary": _lib.VK_LOSS_BINARY, "multilabel": _lib.VK_LOSS_MULTILABEL, "multiclass": _lib.VK_LOSS_MULTICLASS}
 MAX_CLASSES = 16
 
@@ -248,11 +248,11 @@ class CrossEntropyLoss(_Term):
 
 
 def LovaszLoss(*a, **k):
-    raise NotImplementedError("LovaszLoss needs a device sort and is not implemented")
+    raise NotImplementedError("LovaszLoss needs a device sort and is not implemented here: use vk.lovasz.LovaszLoss")
 
 
 def MCCLoss(*a, **k):
-    raise NotImplementedError("MCCLoss is not implemented")
+    raise NotImplementedError("MCCLoss is not implemented here: use vk.lovasz.MCCLoss")
 
 
 class _SegLossFn(torch.autograd.Function):
@@ -310,6 +310,8 @@ class LossSum(_Algebra, nn.Module):
         if len(modes) > 1:
             raise ValueError("LossSum: terms disagree on mode: " + ", ".join("%s is %r" % (type(t).__name__, m) for m, t in modes.items()))
         mode = next(iter(modes), None)
+        if mode != "binary" and "mcc" in seen and mode is not None:
+            raise ValueError("LossSum: MCCLoss is a binary loss and cannot join a sum of mode %r" % (mode,))
         if mode == "multiclass" and any(t.bce for _, t in terms):
             raise ValueError("LossSum: a BCE term cannot join a sum of mode 'multiclass' (use CrossEntropyLoss / SoftCrossEntropyLoss)")
         igns = {}
@@ -378,6 +380,8 @@ class LossSum(_Algebra, nn.Module):
                 c.focal_has_alpha = 0 if o["alpha"] is None else 1
                 c.focal_alpha = 0.0 if o["alpha"] is None else o["alpha"]
                 c.focal_gamma = o["gamma"]
+            elif k == "mcc":
+                c.mcc_eps = o["eps"]
             else:
                 setattr(c, k + "_smooth", o["smooth"])
                 setattr(c, k + "_eps", o["eps"])

@@ -511,10 +511,15 @@ class Unet(nn.Module):
         DiceLoss("multiclass"); a label outside [0, C) makes the result NaN).  With classes > 1 the mode must be
         given.
         ``loss``: a ``vk.seglosses`` term or sum instead of ``mode`` (the two exclude each other): the same step with that loss
-        (vk_unet_loss_cfg); returns a device tensor [total, pix, focal, dice, jaccard, tversky] of a buffer of its own."""
+        (vk_unet_loss_cfg); returns a device tensor [total, pix, focal, dice, jaccard, tversky] of a buffer of its own.  A
+        ``vk.lovasz.LovaszLoss`` or ``vk.lovasz.LossSum`` runs vk_unet_loss_lovasz instead and returns
+        [total, pix, focal, dice, jaccard, tversky, mcc, lovasz]."""
         if loss is not None:
             if mode is not None:
                 raise ValueError("loss_and_backward: give mode= or loss=, not both")
+            from . import lovasz
+            if isinstance(loss, lovasz._LovaszAlgebra):
+                return self._loss_lovasz_and_backward(x, y, grad_scale, dtype, loss._as_lovasz_sum())
             return self._loss_cfg_and_backward(x, y, grad_scale, dtype, loss)
         if mode is None:
             if self.classes != 1:
@@ -576,6 +581,36 @@ class Unet(nn.Module):
         self.last_logits = logits
         S.last_components = out[:6]
         return out[:6]
+
+
+    def _loss_lovasz_and_backward(self, x, y, grad_scale, dtype, S) -> torch.Tensor:
+        lcfg = S.lovasz_cfg(self.classes)
+        scfg = S.seg_cfg(self.classes)
+        self._check_input(x)
+        mask = self._trainable_mask()
+        if not any(mask):
+            raise VkError("loss_and_backward: no parameter requires grad (every tensor is frozen)")
+        N, _, H, W = x.shape
+        multiclass = lcfg.mode == _lib.VK_LOSS_MULTICLASS
+        if multiclass:
+            if tuple(y.shape) != (N, H, W) or y.dtype != torch.int64:
+                raise ValueError("loss_and_backward(loss=<multiclass>): target must be int64 [N,H,W], got %s %s" % (y.dtype, tuple(y.shape)))
+        elif y.dim() != 4 or y.shape[0] != N or y.shape[1] not in (1, self.classes) or tuple(y.shape[2:]) != (H, W):
+            raise ValueError("loss_and_backward(loss=...): target must be [N,%d,H,W], got %s" % (self.classes, tuple(y.shape)))
+        plan = self.plan_for(N, H if H == W else (H, W), dtype or self.compute_dtype, True)
+        logits = self._run_forward(plan, x, True)
+        y = y.detach().contiguous() if multiclass else y.detach().float().expand(N, self.classes, H, W).contiguous()
+        out = getattr(plan, "lovasz_loss_out", None)
+        if out is None:
+            out = plan.lovasz_loss_out = torch.zeros(16, dtype=torch.float32, device=logits.device)
+            plan.lovasz_pick = torch.tensor([0, 1, 2, 3, 4, 5, 7, 8], dtype=torch.int64, device=logits.device)
+        ws = S.workspace(lcfg, N, self.classes, H * W, logits.device)
+        check(lib().vk_unet_loss_lovasz(plan.h, scfg, lcfg, S.w, logits.data_ptr(), y.data_ptr(), ws.data_ptr(), ws.numel(),
+                                        out.data_ptr(), float(grad_scale), _lib.current_stream()), "vk_unet_loss_lovasz")
+        self._run_backward(plan, None, mask)
+        self.last_logits = logits
+        S.last_components = out.index_select(0, plan.lovasz_pick)
+        return S.last_components
 
 
 def build_model(encoder: str = "resnet34", weights: Optional[str] = "imagenet") -> Unet:

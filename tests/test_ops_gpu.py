@@ -17,6 +17,7 @@ L_ = vk._lib
 
 DT = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}
 REPL = 32       # VK_STATS_REPLICAS in include/vk_unet.h
+STATS_SPAN = 512    # most stored values that one fp32 BatchNorm partial sum covers before it goes to fp64 (StreamCfg::RS = 32 rows x 16)
 
 
 def dev():
@@ -146,20 +147,20 @@ def gen(*shape, seed=0, scale=1.0):
 
 # ------------------------------------------------------------------------------------------------ conv forward
 CONV_CASES = [
-    # name, N, H, C, K, R, stride, pad, affine
-    ("l1_3x3", 2, 24, 64, 64, 3, 1, 1, True),
-    ("l2_s2", 2, 24, 64, 128, 3, 2, 1, False),
-    ("l3_s2_affine", 2, 20, 128, 256, 3, 2, 1, True),
-    ("l4_s2_ragged", 1, 18, 256, 512, 3, 2, 1, False),
-    ("s2_wide", 1, 70, 64, 128, 3, 2, 1, False),
-    ("l2_down1x1", 2, 24, 64, 128, 1, 2, 0, False),
-    ("l4_3x3", 1, 8, 512, 512, 3, 1, 1, True),
-    ("dec3_c2", 1, 40, 32, 32, 3, 1, 1, True),
-    ("dec4_c2_smallC", 1, 40, 16, 16, 3, 1, 1, True),
-    ("odd_edges", 3, 13, 32, 48, 3, 1, 1, True),
-    ("l2_body", 2, 40, 128, 128, 3, 1, 1, True),
-    ("l3_ragged", 1, 27, 256, 256, 3, 1, 1, True),
-    ("k192", 1, 20, 64, 192, 3, 1, 1, False),
+    # name, N, H, W, C, K, R, stride, pad, affine   (more than a third of the maps are not square, in both orientations)
+    ("l1_3x3", 2, 24, 40, 64, 64, 3, 1, 1, True),
+    ("l2_s2", 2, 24, 24, 64, 128, 3, 2, 1, False),
+    ("l3_s2_affine", 2, 20, 28, 128, 256, 3, 2, 1, True),
+    ("l4_s2_ragged", 1, 18, 18, 256, 512, 3, 2, 1, False),
+    ("s2_wide", 1, 70, 70, 64, 128, 3, 2, 1, False),
+    ("l2_down1x1", 2, 24, 16, 64, 128, 1, 2, 0, False),
+    ("l4_3x3", 1, 8, 12, 512, 512, 3, 1, 1, True),
+    ("dec3_c2", 1, 40, 40, 32, 32, 3, 1, 1, True),
+    ("dec4_c2_smallC", 1, 40, 24, 16, 16, 3, 1, 1, True),
+    ("odd_edges", 3, 13, 21, 32, 48, 3, 1, 1, True),
+    ("l2_body", 2, 40, 40, 128, 128, 3, 1, 1, True),
+    ("l3_ragged", 1, 27, 19, 256, 256, 3, 1, 1, True),
+    ("k192", 1, 20, 20, 64, 192, 3, 1, 1, False),
 ]
 
 
@@ -167,11 +168,11 @@ CONV_CASES = [
 @pytest.mark.parametrize("case", CONV_CASES, ids=[c[0] for c in CONV_CASES])
 def test_conv_fwd(case, dtn, conv_path):
     dt = DT[dtn]
-    _, N, H, Cc, K, R, stride, pad, affine = case
+    _, N, H, W, Cc, K, R, stride, pad, affine = case
     if (conv_path.startswith("tile_alt") and K < 128) or (conv_path == "tile_persist" and K >= 128):
         pytest.skip("alternative tile shapes exist for K >= 128 only")
-    Ho = (H + 2 * pad - R) // stride + 1
-    x = gen(N, Cc, H, H, seed=1)
+    Ho, Wo = (H + 2 * pad - R) // stride + 1, (W + 2 * pad - R) // stride + 1
+    x = gen(N, Cc, H, W, seed=1)
     w = gen(K, Cc, R, R, seed=2, scale=(2.0 / (Cc * R * R)) ** 0.5)
     xd = to_nhwc(x, dt)
     wd = D(w.permute(0, 2, 3, 1).contiguous().to(dt))
@@ -183,9 +184,9 @@ def test_conv_fwd(case, dtn, conv_path):
         sc, sh = D(sc_c), D(sh_c)
         v = rnd(torch.relu(v * sc_c.view(1, -1, 1, 1) + sh_c.view(1, -1, 1, 1)), dt)
     ref = F.conv2d(v.double(), rnd(w, dt).double(), stride=stride, padding=pad).float()
-    y = torch.full((N, Ho, Ho, K), float("nan"), dtype=dt, device=dev())
+    y = torch.full((N, Ho, Wo, K), float("nan"), dtype=dt, device=dev())
     stats = torch.zeros(REPL * 2 * K, dtype=torch.float64, device=dev())
-    d = conv_desc(dt, N, H, H, Ho, Ho, K, R, stride, pad, 0, mk_src(xd, Cc, 0, sc, sh, 1 if affine else 0))
+    d = conv_desc(dt, N, H, W, Ho, Wo, K, R, stride, pad, 0, mk_src(xd, Cc, 0, sc, sh, 1 if affine else 0))
     conv_run(d, wd, y, stats=stats, plain=conv_path == "tap")
     torch.cuda.synchronize()
     got = from_nhwc(y)
@@ -197,6 +198,11 @@ def test_conv_fwd(case, dtn, conv_path):
     yy = from_nhwc(y).double()
     assert torch.allclose(s[:K], yy.sum(dim=(0, 2, 3)), rtol=1e-4, atol=1e-3 * yy.abs().max().item() * yy[:, 0].numel() ** 0.5)
     assert torch.allclose(s[K:], (yy * yy).sum(dim=(0, 2, 3)), rtol=1e-4, atol=1e-3)
+    # derived: the sums are fp32 partials of at most STATS_SPAN stored values (one 128-pixel tile; one strip of 32 rows x 16 columns in the
+    # streaming kernels), in any order, then fp64 atomics; n fp32 additions are off by at most (n - 1) 2^-24 sum |v|, and each square by
+    # one more rounding
+    assert bool(((s[:K] - yy.sum(dim=(0, 2, 3))).abs() <= (STATS_SPAN - 1) * 2.0 ** -24 * yy.abs().sum(dim=(0, 2, 3))).all())
+    assert bool(((s[K:] - (yy * yy).sum(dim=(0, 2, 3))).abs() <= STATS_SPAN * 2.0 ** -24 * (yy * yy).sum(dim=(0, 2, 3))).all())
 
 
 SPLITK_CASES = [
@@ -331,18 +337,19 @@ def test_stem_fwd(dtn, S, path, monkeypatch):
 
 # ------------------------------------------------------------------------------------------------ dgrad
 DGRAD_CASES = [
-    ("s1_3x3", 2, 24, 64, 64, 3, 1, 1),
-    ("s2_3x3", 2, 24, 64, 128, 3, 2, 1),
-    ("s2_3x3_parity_tiles", 2, 32, 64, 128, 3, 2, 1),      # 16x16 pixels per parity class = whole 128-pixel tiles: tap skipping active
-    ("s2_3x3_c256", 1, 64, 128, 256, 3, 2, 1),
-    ("s2_3x3_ragged", 1, 26, 256, 512, 3, 2, 1),           # 13 x 13 dz: partial 8 x 16 tiles in both directions
-    ("s2_3x3_wide", 1, 72, 64, 128, 3, 2, 1),              # three tile columns
-    ("s2_1x1", 2, 24, 64, 128, 1, 2, 0),
-    ("s2_1x1_parity_tiles", 2, 32, 64, 128, 1, 2, 0),
-    ("k16", 1, 40, 32, 16, 3, 1, 1),      # reduction over 16 output channels (small-C mode)
-    ("k32", 1, 40, 128, 32, 3, 1, 1),
-    ("c128", 2, 24, 128, 128, 3, 1, 1),
-    ("c384_k128", 1, 36, 384, 128, 3, 1, 1),
+    # name, N, H, W, C, K, R, stride, pad   (H, W: the map of dx; half of them are not square)
+    ("s1_3x3", 2, 24, 40, 64, 64, 3, 1, 1),
+    ("s2_3x3", 2, 24, 32, 64, 128, 3, 2, 1),
+    ("s2_3x3_parity_tiles", 2, 32, 32, 64, 128, 3, 2, 1),  # 16x16 pixels per parity class = whole 128-pixel tiles: tap skipping active
+    ("s2_3x3_c256", 1, 64, 64, 128, 256, 3, 2, 1),
+    ("s2_3x3_ragged", 1, 26, 30, 256, 512, 3, 2, 1),       # 13 x 15 dz: partial 8 x 16 tiles in both directions
+    ("s2_3x3_wide", 1, 72, 72, 64, 128, 3, 2, 1),          # three tile columns
+    ("s2_1x1", 2, 24, 16, 64, 128, 1, 2, 0),
+    ("s2_1x1_parity_tiles", 2, 32, 32, 64, 128, 1, 2, 0),
+    ("k16", 1, 40, 24, 32, 16, 3, 1, 1),      # reduction over 16 output channels (small-C mode)
+    ("k32", 1, 40, 40, 128, 32, 3, 1, 1),
+    ("c128", 2, 24, 36, 128, 128, 3, 1, 1),
+    ("c384_k128", 1, 36, 36, 384, 128, 3, 1, 1),
 ]
 
 
@@ -350,20 +357,20 @@ DGRAD_CASES = [
 @pytest.mark.parametrize("case", DGRAD_CASES, ids=[c[0] for c in DGRAD_CASES])
 def test_conv_dgrad(case, dtn, conv_path):
     dt = DT[dtn]
-    _, N, H, Cc, K, R, stride, pad = case
+    _, N, H, W, Cc, K, R, stride, pad = case
     if (conv_path.startswith("tile_alt") and Cc < 128) or (conv_path == "tile_persist" and Cc >= 128):
         pytest.skip("alternative tile shapes exist for >= 128 output channels only")
-    Ho = (H + 2 * pad - R) // stride + 1
+    Ho, Wo = (H + 2 * pad - R) // stride + 1, (W + 2 * pad - R) // stride + 1
     w = gen(K, Cc, R, R, seed=21, scale=(2.0 / (K * R * R)) ** 0.5)
-    dz = gen(N, K, Ho, Ho, seed=22)
-    xin = torch.zeros(N, Cc, H, H, dtype=torch.float64, requires_grad=True)
+    dz = gen(N, K, Ho, Wo, seed=22)
+    xin = torch.zeros(N, Cc, H, W, dtype=torch.float64, requires_grad=True)
     out = F.conv2d(xin, rnd(w, dt).double(), stride=stride, padding=pad)
     out.backward(rnd(dz, dt).double())
     ref = xin.grad.float()
     dzd = to_nhwc(dz, dt)
     wt = D(w.permute(1, 2, 3, 0).contiguous().to(dt))     # [C][R][S][K]
-    dx = torch.full((N, H, H, Cc), float("nan"), dtype=dt, device=dev())
-    d = conv_desc(dt, N, Ho, Ho, H, H, Cc, R, stride, pad, 1, mk_src(dzd, K))
+    dx = torch.full((N, H, W, Cc), float("nan"), dtype=dt, device=dev())
+    d = conv_desc(dt, N, Ho, Wo, H, W, Cc, R, stride, pad, 1, mk_src(dzd, K))
     conv_run(d, wt, dx, plain=conv_path == "tap")
     torch.cuda.synchronize()
     got = from_nhwc(dx)
@@ -510,19 +517,20 @@ def test_conv_dgrad_fused_block_tail(dtn, shape, persist):
 
 # ------------------------------------------------------------------------------------------------ wgrad
 WGRAD_CASES = [
-    ("l1", 2, 24, 64, 64, 3, 1, 1),
-    ("l2_s2", 2, 24, 64, 128, 3, 2, 1),
-    ("l3_s2_ragged", 1, 26, 128, 256, 3, 2, 1),            # 13 x 13 dz: partial 8 x 16 tiles
-    ("l4_s2", 1, 20, 256, 512, 3, 2, 1),
-    ("s2_wide", 1, 72, 32, 64, 3, 2, 1),                   # three tile columns, one 32-channel chunk
-    ("l2_1x1", 2, 24, 64, 128, 1, 2, 0),
-    ("l3", 1, 16, 256, 256, 3, 1, 1),
-    ("dec3_c2", 1, 40, 32, 32, 3, 1, 1),
-    ("dec4_c1", 1, 40, 32, 16, 3, 1, 1),
-    ("dec4_c2", 1, 40, 16, 16, 3, 1, 1),
-    ("dec3_c1", 1, 24, 128, 32, 3, 1, 1),
-    ("odd", 3, 13, 32, 48, 3, 1, 1),
-    ("l2_body", 2, 20, 128, 128, 3, 1, 1),
+    # name, N, H, W, C, K, R, stride, pad   (more than half of the maps are not square)
+    ("l1", 2, 24, 40, 64, 64, 3, 1, 1),
+    ("l2_s2", 2, 24, 32, 64, 128, 3, 2, 1),
+    ("l3_s2_ragged", 1, 26, 22, 128, 256, 3, 2, 1),        # 13 x 11 dz: partial 8 x 16 tiles
+    ("l4_s2", 1, 20, 20, 256, 512, 3, 2, 1),
+    ("s2_wide", 1, 72, 72, 32, 64, 3, 2, 1),               # three tile columns, one 32-channel chunk
+    ("l2_1x1", 2, 24, 16, 64, 128, 1, 2, 0),
+    ("l3", 1, 16, 16, 256, 256, 3, 1, 1),
+    ("dec3_c2", 1, 40, 24, 32, 32, 3, 1, 1),
+    ("dec4_c1", 1, 40, 40, 32, 16, 3, 1, 1),
+    ("dec4_c2", 1, 40, 56, 16, 16, 3, 1, 1),
+    ("dec3_c1", 1, 24, 24, 128, 32, 3, 1, 1),
+    ("odd", 3, 13, 21, 32, 48, 3, 1, 1),
+    ("l2_body", 2, 20, 20, 128, 128, 3, 1, 1),
 ]
 
 
@@ -549,10 +557,10 @@ def wgrad_path(request, monkeypatch):
 @pytest.mark.parametrize("case", WGRAD_CASES, ids=[c[0] for c in WGRAD_CASES])
 def test_conv_wgrad(case, dtn, wgrad_path):
     dt = DT[dtn]
-    _, N, H, Cc, K, R, stride, pad = case
-    Ho = (H + 2 * pad - R) // stride + 1
-    x = gen(N, Cc, H, H, seed=41)
-    dz = gen(N, K, Ho, Ho, seed=42)
+    _, N, H, W, Cc, K, R, stride, pad = case
+    Ho, Wo = (H + 2 * pad - R) // stride + 1, (W + 2 * pad - R) // stride + 1
+    x = gen(N, Cc, H, W, seed=41)
+    dz = gen(N, K, Ho, Wo, seed=42)
     sc_c = 0.5 + torch.rand(Cc, generator=torch.Generator().manual_seed(43))
     sh_c = gen(Cc, seed=44, scale=0.3)
     v = rnd(torch.relu(rnd(x, dt) * sc_c.view(1, -1, 1, 1) + sh_c.view(1, -1, 1, 1)), dt)
@@ -561,7 +569,7 @@ def test_conv_wgrad(case, dtn, wgrad_path):
     ref = wv.grad.float()
     xd, dzd = to_nhwc(x, dt), to_nhwc(dz, dt)
     dw = torch.zeros(K, R, R, Cc, dtype=torch.float32, device=dev())
-    d = conv_desc(dt, N, H, H, Ho, Ho, K, R, stride, pad, 0, mk_src(xd, Cc, 0, D(sc_c), D(sh_c), 1))
+    d = conv_desc(dt, N, H, W, Ho, Wo, K, R, stride, pad, 0, mk_src(xd, Cc, 0, D(sc_c), D(sh_c), 1))
     vk._lib.check(vk.lib().vk_conv_wgrad(C.byref(d), dzd.data_ptr(), dw.data_ptr(), WS_.data_ptr() if WS_ is not None else None, WS_.numel() if WS_ is not None else 0, st()))
     torch.cuda.synchronize()
     got = dw.cpu().permute(0, 3, 1, 2)

@@ -1441,6 +1441,34 @@ int conv_dgrad_into(vk_unet* h, ConvL& c, ConvL& into, bool* fused, hipStream_t 
   return vk_conv_fwd(&d, dgrad_weights(h, c), into.g, nullptr, 0, 0, nullptr, st);
 }
 
+// BatchNorm-backward apply, data gradient into `into.g` (with the BN+ReLU backward reduce of `into`) and weight gradient of conv c in one
+// kernel; c.g holds the pre-reduced masked gradient.  *state: 0 nothing enqueued (the kernel does not cover the layer), 1 all done,
+// 2 the entry point declined after the coefficient launch: the apply pass ran instead (c.g holds dz), data and weight gradient are left.
+int conv_bwd_onepass(vk_unet* h, ConvL& c, ConvL& into, int* state, hipStream_t st) {
+  *state = 0;
+  BnL& b = h->bns[c.bn];
+  vk_conv_desc d = conv_desc(h, c, to_src(bn_act(h, into)), null_src());
+  if (d.dtype == VK_F32 || d.R != 3 || d.S != 3 || d.stride != 1 || d.pad != 1 || d.src0.up || d.src0.C != d.K || (d.K != 16 && d.K != 32)) return VK_OK;
+  static const int maxc = getenv("VK_BN_APPLY_FUSED_MAXC") ? atoi(getenv("VK_BN_APPLY_FUSED_MAXC")) : VK_BN_APPLY_FUSED_MAXC_DEFAULT;
+  if (!frozen(h, b) && c.K <= maxc) return VK_OK;            // that switch derives the coefficients inside the apply kernel
+  // the coefficient launch of bn_bwd_phase2 (frozen statistics: (a, 0, 0) is in b.coef since the forward)
+  if (frozen(h, b)) {
+    if (trains(h, b.g_t) || trains(h, b.b_t))
+      RET_IF(vk_bn_bwd_coeffs_frozen(c.K, b.bsums, h->params + b.g_off, b.mean, b.invstd, dgamma_of(h, b), dbeta_of(h, b), b.coef, st));
+  } else {
+    RET_IF(vk_bn_bwd_coeffs(c.K, b.bsums, b.count, h->params + b.g_off, b.mean, b.invstd, dgamma_of(h, b), dbeta_of(h, b), b.coef, st));
+  }
+  vk_bnr r = bnr_of(h, into);
+  const int rc = vk_conv_bwd_onepass(&d, c.g, c.z, b.coef, dgrad_weights(h, c), into.g, &r, h->grads + c.w_off, h->ws + h->off_wslab,
+                                     VK_WGRAD_WORKSPACE_BYTES, st);
+  if (rc == VK_ERR_UNSUPPORTED) {
+    *state = 2;
+    return vk_bn_bwd_apply(h->cfg.dtype, (size_t)h->cfg.N * c.Hout * c.Wout, c.K, c.g, c.z, 0, b.scale, b.shift, nullptr, b.coef, c.g, nullptr, 0, st);
+  }
+  *state = rc == VK_OK ? 1 : 0;
+  return rc;
+}
+
 // dx = dgrad(dz of conv c) into y (and y1 for the channel split)
 int conv_dgrad(vk_unet* h, ConvL& c, void* y, void* y1, int split, int accumulate, hipStream_t st) {
   vk_conv_desc d;
@@ -1492,11 +1520,21 @@ int backward_decoder(vk_unet* h, int i, hipStream_t st) {
   // Order inside a unit: BN backward -> DATA gradient -> weight gradient.  The weight gradient only feeds the optimizer; issued
   // after the data gradient it can run (side stream, vk_unet_set_side_stream) beside the HBM-bound BatchNorm backward of the
   // NEXT layer instead of beside an MFMA-bound data gradient.
-  RET_IF(bn_relu_bwd_inplace(h, c2, h->g_prereduced[d.conv2] != 0, st));
   const bool into1 = need_from(h, bn1.rank);
   bool fused1 = false;
-  if (into1) RET_IF(conv_dgrad_into(h, c2, c1, &fused1, st));
-  if (trains(h, c2.w_t)) RET_IF(conv_wgrad(h, c2, to_src(bn_act(h, c1)), null_src(), st));
+  // One pass instead of apply + data gradient + weight gradient where vk_conv_bwd_onepass covers the layer (conv2 of decoder blocks
+  // 3 / 4): dz is formed in the kernel and never stored.  VK_NO_ONEPASS=1 (read per launch): the three launches.
+  int onepass = 0;
+  if (h->g_prereduced[d.conv2] && into1 && trains(h, c2.w_t) && h->cfg.dtype != VK_F32 && !h->side && !on_1x1(c2) && !getenv("VK_NO_ONEPASS") &&
+      !getenv("VK_NO_BNR_FUSION"))
+    RET_IF(conv_bwd_onepass(h, c2, c1, &onepass, st));
+  if (onepass == 1) {
+    fused1 = true;
+  } else {
+    if (onepass == 0) RET_IF(bn_relu_bwd_inplace(h, c2, h->g_prereduced[d.conv2] != 0, st));
+    if (into1) RET_IF(conv_dgrad_into(h, c2, c1, &fused1, st));
+    if (trains(h, c2.w_t)) RET_IF(conv_wgrad(h, c2, to_src(bn_act(h, c1)), null_src(), st));
+  }
   if (i > 0) h->g_prereduced[h->decs[i - 1].conv2] = 0;
   if (!into1) return VK_OK;
   // conv1 unit

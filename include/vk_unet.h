@@ -99,7 +99,9 @@ int vk_prof_collect(char* buf, size_t buflen);
 /* One input source of a convolution gather.  The convolution reads a *virtual* input
  *   V[n][h][w][c] = act( src[n][h >> up][w >> up][c] * scale[c] + shift[c] )
  * i.e. nearest-x2 upsample (up=1), train/eval BatchNorm apply (scale/shift != NULL) and ReLU (relu=1)
- * are fused into the operand load; zero padding is applied AFTER that transform. */
+ * are fused into the operand load; zero padding is applied AFTER that transform.
+ * relu is honoured only together with scale / shift: a source with scale == NULL is read as it is (identity), whatever relu says —
+ * every kernel applies the ReLU inside its affine prologue (convolutions, both heads, their weight gradients alike). */
 typedef struct {
   const void* ptr;      /* NHWC, dtype of the conv, [N][H>>up][W>>up][C] */
   int C;                /* channels of this source (multiple of 8; 16 allowed) */
@@ -441,18 +443,27 @@ int vk_head_fwd(vk_dtype dtype, int N, int H, int W, const vk_src* src, const fl
 int vk_dec4_tail_eval(vk_dtype dtype, int N, int H, int W, const vk_src* src, const void* w1_pack, const float* scale1, const float* shift1,
                       const void* w2_plain, const float* scale2, const float* shift2, const float* head_w9x16, const float* head_bias,
                       float* logits, void* stream);
-/* workspace (optional, VK_HEAD_WORKSPACE_BYTES is always enough): per-workgroup partial weight gradients that a second launch
- * adds in workgroup order -> dw / dbias are bit-reproducible; NULL: fp32 atomics */
+/* dy [N][H][W][16] (element type) is WRITTEN, dw9x16 / dbias are ADDED to (+=).
+ * workspace (optional, VK_HEAD_WORKSPACE_BYTES is always enough): per-workgroup partial weight gradients (rows of 148 floats) that a
+ * second launch adds in workgroup order -> dw / dbias are bit-reproducible; NULL (or less than one row): fp32 atomics.  A smaller
+ * workspace is used as it is: the grid shrinks to the rows it holds and every workgroup walks more tiles. */
 #define VK_HEAD_WORKSPACE_BYTES (1024u * 148u * 4u)
 int vk_head_bwd(vk_dtype dtype, int N, int H, int W, const vk_src* src, const float* w9x16, const float* dlogits,
                 void* dy, float* dw9x16, float* dbias, void* workspace, size_t workspace_bytes, void* stream);
-/* same, with the BatchNorm+ReLU backward reduce of the head's input layer fused into the dy kernel (see vk_bnr) */
+/* same, with the BatchNorm+ReLU backward reduce of the head's input layer fused into the dy kernel (see vk_bnr; mask and accumulate
+ * are not used here).  The ReLU mask is [bnr->z * bnr->scale + bnr->shift > 0] on every route, whatever src->relu says (src->relu
+ * only decides what the weight gradient sees); bnr may name a tensor other than the head's source.  The 16-bit types run one
+ * matrix-core kernel when bnr names the head's own source and coefficients (the same pointers), which rounds dlogits and the filter
+ * to the element type; every other combination, and VK_HEAD_NO_MFMA in the environment, runs the two fp32 kernels. */
 int vk_head_bwd_fused(vk_dtype dtype, int N, int H, int W, const vk_src* src, const float* w9x16, const float* dlogits,
                       void* dy, float* dw9x16, float* dbias, const vk_bnr* bnr, void* workspace, size_t workspace_bytes, void* stream);
 
 /* loss = mean BCE-with-logits + binary Dice (smp defaults: batch-global, smooth 0, eps 1e-7).
- * sums: double[8] scratch (zeroed by the call).  loss_out[0] = w_bce*bce + w_dice*dice, [1] = bce, [2] = dice.
- * dlogits (optional) = grad_scale * d(loss_out[0])/dlogits. */
+ * sums: double[8] scratch (zeroed by the call); afterwards sums[0..3] = {sum of the BCE terms, sum p*y, sum p, sum y} over all
+ * elements (p = 1 / (1 + expf(-x)); fp32 per thread, fp64 from there on) and sums[4..6] hold the gradient coefficients.
+ * loss_out[0] = w_bce*bce + w_dice*dice, [1] = bce, [2] = dice; dice = (1 - 2 sum p*y / max(sum p + sum y, 1e-7)) [sum y > 0].
+ * dlogits (optional; NULL: nothing is written) = grad_scale * d(loss_out[0])/dlogits.  16-byte loads when both logits and target are
+ * 16-byte aligned, element loads otherwise: any count and alignment is accepted. */
 int vk_bce_dice_loss(size_t count, const float* logits, const float* target, double* sums, float* loss_out,
                      float* dlogits, float grad_scale, float w_bce, float w_dice, void* stream);
 
@@ -593,7 +604,8 @@ int vk_seg_metrics_multi(int mode, int n_images, int C, size_t per_image, const 
 
 /* AdamW (decoupled decay) over a flat fp32 parameter buffer; optionally emits the 16-bit working copy.
  * inv_scale multiplies the gradient first (GradScaler unscale / data-parallel averaging).
- * found_inf (optional int*): when *found_inf != 0 on the device the step is skipped. */
+ * found_inf (optional int*): when *found_inf != 0 on the device the step is skipped: param, the moments and lowp_copy stay unwritten.
+ * lowp_copy (optional) receives the updated parameters rounded to lowp_dtype (VK_BF16 / VK_F16); with VK_F32 it is not written. */
 int vk_adamw_step(size_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr,
                   float beta1, float beta2, float eps, float weight_decay, int step, float inv_scale,
                   const int* found_inf, void* lowp_copy, vk_dtype lowp_dtype, void* stream);
@@ -607,7 +619,9 @@ int vk_amp_check_inf(size_t n, const float* grad, int* found_inf, void* stream);
  * vk_amp_unscale_check = torch._amp_foreach_non_finite_check_and_unscale_ over the ONE flat gradient buffer:
  *   grad *= *inv_scale (device fp32; NULL or a value of exactly 1 leaves the buffer unwritten), *found_inf = 1.0f if any
  *   element is inf / nan (never cleared here: the caller zeroes it, as GradScaler does).  n % 4 == 0, grad 16-byte aligned.
- * vk_adamw_step_amp = vk_adamw_step with everything step-dependent read on the device: *found_inf != 0 skips the update and
+ *   The product is IEEE: a result below 2^-126 is rounded to the subnormal grid, not flushed to zero.
+ * vk_adamw_step_amp = vk_adamw_step with everything step-dependent read on the device: *found_inf != 0 (the test is `!= 0.0f`: 1, -1
+ *   and NaN all skip) skips the update (param, moments and lowp_copy unwritten) and
  *   leaves *step_count (int32) as it is — GradScaler does not call optimizer.step() on an overflow; otherwise *step_count is
  *   incremented first and drives the bias corrections, and the gradient is multiplied by inv_scale / *grad_scale
  *   (grad_scale NULL: by inv_scale).  scratch4: float[4] device scratch owned by the caller. */

@@ -290,8 +290,11 @@ typedef struct {
   int open_iter;        /* OPEN_ITER */
   int close_iter;       /* CLOSE_ITER */
   int min_area;         /* max(200, int(MIN_AREA_FRAC * h * w)) in the reference (ui_infer_rectangle.py:322) */
-  int max_components;   /* capacity of the per-map detection list (further kept components stay in `clean` and in `counts`) */
+  int max_components;   /* capacity of the per-map detection list, 1..4096 (further kept components stay in `clean` and in `counts`) */
 } vk_geom_desc;
+/* Limits: h 1..4096, w 1..16384, h * w < 2^30, open_iter / close_iter 0..16 (ignored when morph_kernel is 1), min_area >= 1.  A map
+ * of one row, one column or one pixel is valid.  Pixels outside the map never win an erosion or a dilation.  NaN compares as
+ * background, +-0 as foreground only for bin_thresh <= 0; denormal probabilities are compared as they are. */
 
 typedef struct {
   int label;            /* connected-component id as cv2 / scipy number them: 1 + raster rank of the component's first pixel */
@@ -300,14 +303,27 @@ typedef struct {
   float cx, cy;         /* rectangle centre */
   float rw, rh;         /* side lengths: along the supporting hull edge / across it */
   float ux, uy;         /* unit direction of that edge */
-  int hull_n;           /* convex-hull vertices of the component */
-  int reserved;
+  int hull_n;           /* convex-hull vertices of the component (strictly convex ones; 1 for one pixel, 2 for a straight one-pixel line) */
+  int reserved;         /* written as 0 */
   double d1, d2, d_mean;/* diagonals of the int32 box (longest pair first) and their mean, float64 as numpy computes them */
 } vk_geom_det;
 
 int64_t vk_geom_workspace_bytes(const vk_geom_desc* d, int batch);      /* < 0: bad descriptor */
 /* prob: float32 [batch][h][w] in [0,1] (device).  clean: uint8 [batch][h][w] in {0,255}.  dets: [batch][max_components], filled in
- * label order (the host sorts by area like ui_infer_rectangle.py:379).  counts: int32 [batch] = kept components per map. */
+ * label order (the host sorts by area like ui_infer_rectangle.py:379).  counts: int32 [batch] = kept components per map.
+ *
+ * counts[b] is the number of components with area >= min_area, also when it exceeds max_components: then the list holds the first
+ * max_components of them in label order (raster order of each component's first pixel) and `clean` still shows all of them.  Only the
+ * slots 0 .. min(counts[b], max_components) - 1 of a map are written; every byte of the slots above, and nothing outside `clean`,
+ * `dets`, `counts` and the first vk_geom_workspace_bytes() bytes of the workspace, is left as the caller had it.  The workspace need
+ * not be cleared.
+ *
+ * Degenerate hulls.  One pixel (hull_n 1): all four corners are the pixel, cx, cy its coordinates, rw = rh = 0, (ux, uy) = (1, 0),
+ * d1 = d2 = d_mean = 0.  Two hull vertices (hull_n 2, a straight one-pixel line): the rectangle on the segment from the top-most (then
+ * left-most) vertex to the other one: (ux, uy) its unit direction, rw its length, rh the float32 residue of projecting the two points
+ * on the normal (0, or a few 1e-6 on a diagonal), corners 0/3 and 1/2 coincide up to that residue, and d1, d2 are the distances of the
+ * truncated corner pairs as for any other box (for a horizontal or vertical line both equal its length).  The corners are truncated,
+ * not rounded: an end point that comes out as 8.999999 is stored as 8. */
 int vk_geom_minarearect(const vk_geom_desc* d, int batch, const float* prob, uint8_t* clean, vk_geom_det* dets, int* counts,
                         void* workspace, size_t workspace_bytes, void* stream);
 
@@ -326,11 +342,20 @@ typedef struct {
   int n_candidates;
   int contour_n;        /* points of the CHAIN_APPROX_SIMPLE border */
   int hull_n;           /* convex-hull vertices of the dilated component */
-  int flags;            /* bit 0: border longer than the 16,384-point buffer (hull candidate only); bit 1: hull > 4,096 vertices; bit 2: trace aborted */
+  int flags;            /* 0 on an ordinary component; see below */
   double quality;       /* _quad_quality of the chosen candidate */
   double d1, d2, d_mean;
 } vk_geom_quad;
 
+/* flags.  Bit 0 (1): the CHAIN_APPROX_SIMPLE border has more than 16,384 points.  contour_n still reports the full length; the
+ *   border polygon is left out of the epsilon bisection and of the sub-sampling, while the hull's bisection, the hull's sub-sampling
+ *   and the extreme points run as usual: the fit is robust_quadrilateral_from_contour with the hull as its only polygon, and
+ *   n_candidates counts what that produced.
+ * Bit 1 (2): the hull has more than 4,096 vertices; the hull is left out in the same way (with both bits set nothing is fitted).
+ * Bit 2 (4): border following was stopped (more than 2^21 steps, or no neighbour found); handled as bit 0.
+ * A component whose border has fewer than four points (one pixel, a straight one-pixel line without outset) is reported with
+ * valid = 0, branch = 0, n_candidates = 0, a zero box, and its label, area, contour_n and hull_n; so is one for which no step yields
+ * a quadrilateral of area > 10 (branch 0 = none).  counts, the slots that are written and the buffers are as for vk_geom_minarearect. */
 /* as vk_geom_minarearect (same workspace size: vk_geom_workspace_bytes); fit_outset_px 0..3 (reference default 2) */
 int vk_geom_quadrilateral(const vk_geom_desc* d, int fit_outset_px, int batch, const float* prob, uint8_t* clean, vk_geom_quad* dets,
                           int* counts, void* workspace, size_t workspace_bytes, void* stream);

@@ -1,7 +1,7 @@
 """Device geometry post-processing (-m gpu): vk_geom_minarearect through the host mirror of ui_infer_rectangle.py:291-381 against
 oracle/geometry_oracle.py on the same probability maps.  Integer work (clean mask, label ids, areas, hull size, int32 corners) must
-be bit-exact; the float32 rectangle parameters are computed in the same operation order and compared exactly as well (tolerance
-1e-6 relative where stated); diagonals are float64 of exact integers."""
+be bit-exact; the float32 rectangle parameters (centre, size, direction) are computed in the same operation order and compared exactly
+as well; diagonals are float64 of exact integers."""
 import importlib
 
 import numpy as np
@@ -45,8 +45,9 @@ def _compare(prob, dets_g, clean_g, **kw):
         assert dg["area"] == do["area"]
         assert dg["hull_vertices"] == len(do["hull"]), (dg["label"], dg["hull_vertices"], len(do["hull"]))
         assert np.array_equal(dg["box"], do["box"]), (dg["box"], do["box"], do["rect"])
-        assert dg["center"] == pytest.approx(do["center"], rel=1e-6, abs=1e-4)
-        assert dg["size"] == pytest.approx(tuple(float(s) for s in do["rect"]["size"]), rel=1e-6)
+        assert dg["center"] == do["center"]                          # float32 in the same operation order: the same bits
+        assert dg["size"] == tuple(float(s) for s in do["rect"]["size"])
+        assert dg["direction"] == tuple(float(s) for s in do["rect"]["u"])
         assert (dg["d1"], dg["d2"], dg["d_mean"]) == (do["d1"], do["d2"], do["d_mean"])
     return dets_o
 

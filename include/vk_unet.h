@@ -19,6 +19,8 @@
  *   vk_amp_check_inf / vk_amp_unscale_check /
  *   vk_adamw_step_amp ......................... GradScaler unscale + inf check + skipped step  train.py:441-445 (610-611)
  *   vk_adamw_step_amp_segments ................ the same over the tensors that have a gradient (frozen ones are skipped)
+ *   vk_adamw_step_groups / vk_grad_norm_segments  param groups ([dict(params=..., lr=...)]) and clip_grad_norm_ (no reference line:
+ *                                               the standard fine-tuning recipe around train.py:606)
  *   vk_conv_fwd / vk_conv_wgrad / ... ......... the ATen operators the reference dispatches to
  *                                               (conv2d, batch_norm, relu, max_pool2d, interpolate, cat)
  *   vk_conv_fwd_splitk ........................ the same convolutions at batch 1 (predict_mask / Segmenter.infer)
@@ -668,6 +670,35 @@ int vk_adamw_step_amp_segments(int n_segments, const int64_t* segments, int n_bl
                                const float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2, float eps,
                                float weight_decay, int* step_counts, float inv_scale, const float* grad_scale,
                                const float* found_inf, float* scratch, void* stream);
+/* Param groups and global-norm gradient clipping (torch.optim param groups; torch.nn.utils.clip_grad_norm_ without a second write of
+ * the gradient buffer).
+ * vk_adamw_step_groups = vk_adamw_step_amp_segments with the five hyper-parameters of segment s taken from
+ *   groups_host[segment_group[s]] (segment_group: device int32 [n_segments], 0 <= g < n_groups; groups_host: HOST array of n_groups
+ *   entries, 1 <= n_groups <= VK_ADAMW_MAX_GROUPS, copied into the launch, so a scheduler may change it between calls), and with an
+ *   optional clip coefficient: clip_coef (device fp32 scalar, or NULL) multiplies the gradient factor, which is
+ *     (float)(((double)inv_scale / (double)*grad_scale) * (double)*clip_coef)   with grad_scale,
+ *     (float)((double)inv_scale * (double)*clip_coef)                           without,
+ *   and exactly that of vk_adamw_step_amp_segments when clip_coef is NULL.  Tables, counters, scratch (float[4 + 2 n_segments]),
+ *   element arithmetic and skip rule (*found_inf != 0: nothing written, no counter advanced) are those of the call above; with one
+ *   group and no coefficient the results are the same bits.
+ * vk_grad_norm_segments: the norm of inv_scale * grad over the listed segments only (same segment and block tables; gaps and unlisted
+ *   ranges are never read; any segment begin is allowed).  norm_kind VK_NORM_L2: sqrt of the sum of squares, squared and summed in
+ *   double; VK_NORM_INF: the largest |g|, NaN if any element is NaN.  out (device float[2]): out[0] = total = norm * |inv_scale|,
+ *   out[1] = min(max_norm / (total + 1e-6), 1), a NaN kept: torch.nn.utils.clip_grad_norm_'s coefficient, evaluated in double.
+ *   partials: device double[n_blocks] scratch, fully overwritten by every call.  No atomics: the same input gives the same bits.
+ *   max_norm must be a number >= 0. */
+#define VK_ADAMW_MAX_GROUPS 8
+typedef struct {
+  float lr, beta1, beta2, eps, weight_decay;
+} vk_adamw_group;
+int vk_adamw_step_groups(int n_segments, const int64_t* segments, const int32_t* segment_group, int n_blocks, const int32_t* blocks,
+                         float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int n_groups,
+                         const vk_adamw_group* groups_host, int* step_counts, float inv_scale, const float* grad_scale,
+                         const float* found_inf, const float* clip_coef, float* scratch, void* stream);
+#define VK_NORM_L2 0
+#define VK_NORM_INF 1
+int vk_grad_norm_segments(int n_segments, const int64_t* segments, int n_blocks, const int32_t* blocks, const float* grad,
+                          int norm_kind, float inv_scale, float max_norm, double* partials, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Engine level: the whole network as one plan

@@ -17,13 +17,13 @@ from .geometry import (postprocess_minarearect_batch, postprocess_minarearect_mu
 from ._lib import VkError, build, lib  # noqa: F401
 from .losses import BCEDiceLoss, DiceLoss  # noqa: F401
 from .segmetrics import dice_coef, iou_coef, seg_metrics, seg_metrics_device  # noqa: F401
-from .optim import FusedAdamW, GradScaler, adamw_for  # noqa: F401
+from .optim import FusedAdamW, GradScaler, adamw_for, clip_grad_norm_, finetune_groups  # noqa: F401
 from .parallel import GradientReducer, all_reduce_scalars, broadcast_model, make_data_parallel  # noqa: F401
 from .prepost import Segmenter, predict_mask  # noqa: F401
 from .synthetic import seed_everything, synthetic_batch  # noqa: F401
 from .unet import Unet, build_model  # noqa: F401
 
-__all__ = ["Unet", "build_model", "DiceLoss", "BCEDiceLoss", "multiclass", "encoders", "FusedAdamW", "GradScaler", "adamw_for", "GradientReducer",
+__all__ = ["Unet", "build_model", "DiceLoss", "BCEDiceLoss", "multiclass", "encoders", "FusedAdamW", "GradScaler", "adamw_for", "clip_grad_norm_", "finetune_groups", "GradientReducer",
            "make_data_parallel", "broadcast_model", "all_reduce_scalars", "dice_coef", "iou_coef", "seg_metrics", "seg_metrics_device", "synthetic_batch", "seed_everything",
            "VkError", "build", "lib", "losses", "lovasz", "seglosses", "segmetrics", "synthetic", "parallel", "prepost", "Segmenter", "predict_mask", "geometry", "augment", "AugmentSampler", "DeviceDataset",
            "postprocess_minarearect_multi", "postprocess_minarearect_batch", "postprocess_quadrilateral_multi", "postprocess_quadrilateral_batch"]

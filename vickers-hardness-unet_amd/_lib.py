@@ -16,6 +16,8 @@ CSRC = PKG_DIR / "csrc"
 VK_F32, VK_BF16, VK_F16 = 0, 1, 2
 VK_LOSS_BINARY, VK_LOSS_MULTILABEL, VK_LOSS_MULTICLASS = 0, 1, 2
 VK_ENC_RESNET18, VK_ENC_RESNET34, VK_ENC_RESNET50 = 18, 34, 50
+VK_ADAMW_MAX_GROUPS = 8
+VK_NORM_L2, VK_NORM_INF = 0, 1
 
 
 class VkError(RuntimeError):
@@ -82,6 +84,10 @@ class vk_seg_loss_cfg(C.Structure):
 class vk_lovasz_cfg(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("per_image", C.c_int32), ("has_ignore", C.c_int32),
                 ("ignore_index", C.c_int32)]
+
+
+class vk_adamw_group(C.Structure):
+    _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float)]
 
 
 class vk_unet_config(C.Structure):
@@ -178,6 +184,8 @@ SIGNATURES = {
     "vk_adamw_step_amp": (ci, [sz, vp, vp, vp, vp, cf, cf, cf, cf, cf, vp, cf, vp, vp, vp, vp, ci, vp]),
     "vk_adamw_segment_blocks": (ci, [ci, P(i64), P(C.c_int32), ci]),
     "vk_adamw_step_amp_segments": (ci, [ci, vp, ci, vp, vp, vp, vp, vp, cf, cf, cf, cf, cf, vp, cf, vp, vp, vp, vp]),
+    "vk_adamw_step_groups": (ci, [ci, vp, vp, ci, vp, vp, vp, vp, vp, ci, P(vk_adamw_group), vp, cf, vp, vp, vp, vp, vp]),
+    "vk_grad_norm_segments": (ci, [ci, vp, ci, vp, vp, ci, cf, cf, vp, vp, vp]),
     "vk_unet_create": (ci, [P(vk_unet_config), P(vp)]),
     "vk_unet_create_ex": (ci, [P(vk_unet_config), ci, P(vp)]),
     "vk_unet_num_classes": (ci, [vp]),

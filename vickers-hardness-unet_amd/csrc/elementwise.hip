@@ -1292,28 +1292,7 @@ __global__ void k_adamw_prepare(int* __restrict__ step_count, const float* __res
   st[3] = grad_scale ? (float)((double)inv_scale / (double)*grad_scale) : inv_scale;
 }
 
-// one element of k_adamw_segments: k_adamw_dev's expression with its fused multiply-adds spelled out and contraction off.  They are
-// exactly the ones the compiler forms in k_adamw_dev's loop (g*inv - m, m + d*(1 - beta1), gi*((1 - beta2)*gi) + v*beta2,
-// p*(1 - lr*wd) - step*ratio); written as plain source the vectoriser pairs this loop's products into v_pk_mul_f32 instead and
-// rounds them separately.  So the two kernels agree bit for bit (tests/test_frozen_params_gpu.py holds them to it).
-__device__ __forceinline__ float adamw_elem(size_t i, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                            float* __restrict__ v, float lr, float beta1, float beta2, float eps, float wd, float step_size,
-                                            float bc2_sqrt, float inv_scale) {
-#pragma clang fp contract(off)
-  const float gr = g[i];
-  const float gi = gr * inv_scale;
-  const float keep = __builtin_fmaf(-lr, wd, 1.f);                                  // 1 - lr*wd
-  float mi = m[i];
-  mi = __builtin_fmaf(__builtin_fmaf(gr, inv_scale, -mi), 1.f - beta1, mi);        // m + (gi - m)*(1 - beta1)
-  const float vi = __builtin_fmaf(gi, (1.f - beta2) * gi, v[i] * beta2);          // v*beta2 + (1 - beta2)*gi*gi
-  const float denom = sqrtf(vi) / bc2_sqrt + eps;
-  const float pi = __builtin_fmaf(p[i], keep, -(step_size * (mi / denom)));        // p*(1 - lr*wd) - step*(m / denom)
-  p[i] = pi;
-  m[i] = mi;
-  v[i] = vi;
-  return pi;
-}
-
+// adamw_elem (one element of k_adamw_segments, bit for bit k_adamw_dev's loop body) lives in vk_common.h: optim_groups.hip shares it.
 template <typename LT>
 __global__ void k_adamw_dev(size_t n, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                             float lr, float beta1, float beta2, float eps, float wd, const float* __restrict__ st, LT* lowp) {

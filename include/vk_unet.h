@@ -279,6 +279,46 @@ int vk_letterbox_postprocess_mask_multi(const vk_letterbox_desc* d, int C, const
 int vk_letterbox_postprocess_prob_multi(const vk_letterbox_desc* d, int C, int mode, const float* logits, float* probs_chw, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Sliding-window inference at the image's own resolution, with D4 test-time augmentation: the uint8 image is cut into
+ * overlapping T x T tiles on the device, every tile in 1, 2, 4 or 8 views, and the per-tile logits are blended back into one map.
+ * Grid, per axis of length L with stride s = T - overlap: n = 1 if L <= T else ceil((L - T) / s) + 1 origins,
+ * origin[i] = min(i * s, max(L - T, 0)) (the last tile is pulled back flush with the edge; padding only where L < T).  Tile index
+ * t = iy * nx + ix.  View v = 4*tr + 2*fy + fx of a tile A: A_v[i][j] = A[i0][j0] with (a, b) = tr ? (j, i) : (i, j),
+ * i0 = fy ? T-1-a : a, j0 = fx ? T-1-b : b.  view_mask is 0x01 (no augmentation), 0x03 (+ horizontal flip), 0x0f (the four flips) or
+ * 0xff (all of D4); the views of a tile are stored in ascending v.
+ * Both calls check the descriptor on the host first (VK_ERR_ARG and the error string: sizes, 0 <= overlap <= T/2, at most
+ * VK_TILE_MAX_ORIGINS origins per axis and exactly those of the rule above, the view mask), before anything touches the stream or the
+ * outputs.
+ * ---------------------------------------------------------------------------------------------- */
+#define VK_TILE_MAX_ORIGINS 64
+#define VK_TILE_MAX_SIDE 4096
+#define VK_BLEND_PROB 0
+#define VK_BLEND_LOGIT 1
+typedef struct {
+  int h, w;             /* image size */
+  int src_stride;       /* bytes per row of the BGR image (>= 3*w); unused by the blend */
+  int T;                /* tile side, 1..VK_TILE_MAX_SIDE */
+  int overlap;          /* 0..T/2 */
+  int ny, nx;           /* origins per axis */
+  int ys[VK_TILE_MAX_ORIGINS], xs[VK_TILE_MAX_ORIGINS];
+  int view_mask;        /* bit v set = view v present */
+  int pad_value;        /* value 0..255 of the pixels outside the image, applied before the normalisation; unused by the blend */
+  int C;                /* logit planes per tile, 1..16; unused by the pre-processing */
+} vk_tile_desc;
+
+/* uint8 BGR [h][w][3] (device) -> float32 [ntiles*nviews][3][T][T] (tile major, view minor): view map, source pixel or pad_value,
+ * BGR->RGB, ((v/255) - mean) / std with the expressions of vk_letterbox_preprocess (the same bits) */
+int vk_tile_preprocess(const vk_tile_desc* d, const uint8_t* bgr, float* x, void* stream);
+/* logits fp32 [ntiles*nviews][C][T][T] -> out_chw fp32 [C][h][w] and / or mask_chw uint8 {0,255} [C][h][w] (one of them may be NULL).
+ * Per pixel and plane, in this order: the covering tiles in ascending t; per tile q = (1/nviews) * (sum over ascending v of f(logit at
+ * the view's image of the pixel)); a pixel in exactly one tile takes q, otherwise acc += w*q, wsum += w and the value is acc / wsum
+ * with w = w1(ty) * w1(tx), w1(t) = (float)min(t+1, T-t, R) / (float)R, R = overlap (1 when overlap is 0).  No atomics, no fused
+ * multiply-add: the result does not depend on the launch.
+ * mode VK_BLEND_PROB: f = sigmoid, value clipped to [0,1], mask = value >= thresh.  VK_BLEND_LOGIT: f = identity (the blended raw
+ * logits: the mode for multi-class models, whose softmax stays with the caller), mask = sigmoid(value) >= thresh. */
+int vk_tile_blend(const vk_tile_desc* d, int mode, const float* logits, float thresh, float* out_chw, uint8_t* mask_chw, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Geometry post-processing of batched probability maps: what the reference's GUIs do with
  * Segmenter.infer's output to obtain the indentation diagonals — ui_infer_rectangle.py:291-381 postprocess_minarearect_multi
  * (steps 1-3 are shared by ui_infer_quadrilateral.py:446-490): (prob >= bin_thresh) -> morphologyEx OPEN, CLOSE with the

@@ -18,6 +18,8 @@ VK_LOSS_BINARY, VK_LOSS_MULTILABEL, VK_LOSS_MULTICLASS = 0, 1, 2
 VK_ENC_RESNET18, VK_ENC_RESNET34, VK_ENC_RESNET50 = 18, 34, 50
 VK_ADAMW_MAX_GROUPS = 8
 VK_NORM_L2, VK_NORM_INF = 0, 1
+VK_TILE_MAX_ORIGINS, VK_TILE_MAX_SIDE = 64, 4096
+VK_BLEND_PROB, VK_BLEND_LOGIT = 0, 1
 
 
 class VkError(RuntimeError):
@@ -43,6 +45,12 @@ class vk_bnr(C.Structure):
 class vk_letterbox_desc(C.Structure):
     _fields_ = [("h", C.c_int), ("w", C.c_int), ("src_stride", C.c_int), ("size", C.c_int), ("nh", C.c_int),
                 ("nw", C.c_int), ("top", C.c_int), ("left", C.c_int), ("pad_value", C.c_int)]
+
+
+class vk_tile_desc(C.Structure):
+    _fields_ = [("h", C.c_int), ("w", C.c_int), ("src_stride", C.c_int), ("T", C.c_int), ("overlap", C.c_int), ("ny", C.c_int),
+                ("nx", C.c_int), ("ys", C.c_int * VK_TILE_MAX_ORIGINS), ("xs", C.c_int * VK_TILE_MAX_ORIGINS), ("view_mask", C.c_int),
+                ("pad_value", C.c_int), ("C", C.c_int)]
 
 
 class vk_geom_desc(C.Structure):
@@ -137,6 +145,8 @@ SIGNATURES = {
     "vk_letterbox_postprocess_labels": (ci, [P(vk_letterbox_desc), ci, vp, vp, vp]),
     "vk_letterbox_postprocess_mask_multi": (ci, [P(vk_letterbox_desc), ci, vp, cf, vp, vp]),
     "vk_letterbox_postprocess_prob_multi": (ci, [P(vk_letterbox_desc), ci, ci, vp, vp, vp]),
+    "vk_tile_preprocess": (ci, [P(vk_tile_desc), vp, vp, vp]),
+    "vk_tile_blend": (ci, [P(vk_tile_desc), ci, vp, cf, vp, vp, vp]),
     "vk_geom_workspace_bytes": (i64, [P(vk_geom_desc), ci]),
     "vk_geom_minarearect": (ci, [P(vk_geom_desc), ci, vp, vp, vp, vp, vp, sz, vp]),
     "vk_geom_quadrilateral": (ci, [P(vk_geom_desc), ci, ci, vp, vp, vp, vp, vp, sz, vp]),

@@ -113,6 +113,16 @@ def predict_mask(model, bgr: np.ndarray, device=None, img_size: int = 512, thres
     return postprocess_mask(logits[0, 0], meta, thresh).cpu().numpy()
 
 
+def predict_mask_tiled(model, bgr: np.ndarray, device=None, tile: int = 512, overlap: int = 64, tta: str = "none",
+                       thresh: float = 0.5, batch: int = 16) -> np.ndarray:
+    """predict_mask at the image's own resolution: overlapping tile x tile windows (optionally with test-time augmentation) through
+    the model, blended probabilities >= thresh -> uint8 mask {0,255} [h, w] ([C, h, w] for a model with several classes, per-class
+    sigmoid).  See ``Segmenter.infer_tiled``."""
+    from .tiling import run_tiled
+    m = run_tiled(model, bgr, tile, overlap, tta, "prob", batch, thresh=thresh, values=False, device=device)
+    return (m[0] if m.shape[0] == 1 else m).cpu().numpy()
+
+
 class Segmenter:
     """The PyTorch branch of the Qt wrappers' Segmenter (ui_infer_quadrilateral.py:596-711, ui_infer_rectangle.py:455-564):
     `preprocess(img_bgr) -> (inp, meta)` and `infer(img_bgr) -> float32 probability map of the original size`."""
@@ -130,6 +140,21 @@ class Segmenter:
         with torch.no_grad():
             logits = self.model(x)
         return postprocess_prob(logits[0, 0], meta).cpu().numpy()
+
+    def infer_tiled(self, img_bgr: np.ndarray, tile: Optional[int] = None, overlap: int = 64, tta: str = "none", blend: str = "prob",
+                    batch: int = 16) -> np.ndarray:
+        """The image at its own resolution instead of one letterbox: overlapping ``tile`` x ``tile`` windows (default img_size; the
+        last one of an axis is pulled back flush with the edge), each in the views of ``tta`` ("none", "hflip", "flips", "d4"), through
+        the model in chunks of ``batch``, blended with a ramp of ``overlap`` pixels -> float32 [h, w] ([C, h, w] for a model with
+        several classes).  ``blend="prob"`` averages per-class sigmoids; ``blend="logit"`` returns the blended raw logits, which is the
+        only choice for a multi-class (softmax) model.  An image no larger than the tile is one padded tile: test-time augmentation
+        without tiling.  The image is used at scale 1: resizing first and tiling the result is not done here."""
+        if blend == "prob" and getattr(self, "mode", None) == "multiclass":
+            raise NotImplementedError('a multi-class model has no per-tile probabilities to average: use blend="logit" and apply '
+                                      "the softmax to the blended logits")
+        from .tiling import run_tiled
+        out = run_tiled(self.model, img_bgr, self.img_size if tile is None else tile, overlap, tta, blend, batch, device=self.device)
+        return (out[0] if out.shape[0] == 1 else out).cpu().numpy()
 
     def infer_batch(self, images: Sequence[np.ndarray]) -> List[np.ndarray]:
         """Several images through ONE forward pass (the reference runs them one by one)."""

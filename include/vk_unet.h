@@ -227,13 +227,15 @@ int vk_stem_wgrad(vk_dtype dtype, int N, int H, int W, const void* x4, const voi
 int vk_stem_wgrad_bn(vk_dtype dtype, int N, int H, int W, const void* x4, const void* g, const void* z, const float* coef_abc,
                      float* dw_krsc3, void* workspace, size_t workspace_bytes, void* stream);
 /* BatchNorm-backward apply + data gradient + weight gradient of one small-channel convolution in ONE pass over its tensors: 16-bit
- * types, 3x3 stride 1 pad 1, one source with up = 0, (src0.C, K) = (16, 16) or (32, 32); VK_ERR_UNSUPPORTED for everything else (fp32
- * included) before any launch — run vk_bn_bwd_apply, vk_conv_dgrad_fused and vk_conv_wgrad then.
+ * types, 3x3 stride 1 pad 1, one source: up = 0 with (src0.C, K) = (16, 16) or (32, 32), or up = 1 (nearest x2) with (src0.C, K) =
+ * (32, 16) and H, W even; VK_ERR_UNSUPPORTED for everything else (fp32, odd H or W and every other upsampled shape included) before any
+ * launch — run vk_bn_bwd_apply, vk_conv_dgrad_fused and vk_conv_wgrad then.
  * d_fwd: the layer's FORWARD descriptor (src0 = its input z1 with scale / shift / relu).  g: the masked upstream gradient, z: the layer's
  * own convolution output, both [N][H][W][K]; coef_abc = [3][K] from vk_bn_bwd_coeffs / _frozen: the kernel forms
  * dz = a*g + b*z + c (vk_bn_bwd_apply's fp32 expression, rounded to the element type) in LDS and never stores it.  w_dgrad: what
  * vk_conv_dgrad_fused takes for this layer.  y [N][H][W][C] receives g1 = dgrad(dz) * [bn(z1) > 0], bit for bit what vk_bn_bwd_apply +
- * vk_conv_dgrad_fused store; bnr: z = d_fwd->src0.ptr, scale, shift, sums as for vk_conv_dgrad_fused, mask NULL, accumulate 0.
+ * vk_conv_dgrad_fused store; with up = 1 the source z1 and y are [N][H/2][W/2][32] and g1 is the 2x2-pooled data gradient (what
+ * vk_conv_dgrad_fused with pool2 stores); bnr: z = d_fwd->src0.ptr, scale, shift, sums as for vk_conv_dgrad_fused, mask NULL, accumulate 0.
  * dw [K][3][3][C] += the weight gradient; workspace (required, 16-byte aligned, VK_WGRAD_WORKSPACE_BYTES is always enough) holds one
  * partial result per workgroup, added in a fixed order: the same bits on every run. */
 int vk_conv_bwd_onepass(const vk_conv_desc* d_fwd, const void* g, const void* z, const float* coef_abc, const void* w_dgrad, void* y,

@@ -1444,11 +1444,13 @@ int conv_dgrad_into(vk_unet* h, ConvL& c, ConvL& into, bool* fused, hipStream_t 
 // BatchNorm-backward apply, data gradient into `into.g` (with the BN+ReLU backward reduce of `into`) and weight gradient of conv c in one
 // kernel; c.g holds the pre-reduced masked gradient.  *state: 0 nothing enqueued (the kernel does not cover the layer), 1 all done,
 // 2 the entry point declined after the coefficient launch: the apply pass ran instead (c.g holds dz), data and weight gradient are left.
-int conv_bwd_onepass(vk_unet* h, ConvL& c, ConvL& into, int* state, hipStream_t st) {
+// up: `into` is the conv2 of the previous decoder block, read through the nearest-x2 upsample (conv1 of a block without skip source).
+int conv_bwd_onepass(vk_unet* h, ConvL& c, ConvL& into, int up, int* state, hipStream_t st) {
   *state = 0;
   BnL& b = h->bns[c.bn];
-  vk_conv_desc d = conv_desc(h, c, to_src(bn_act(h, into)), null_src());
-  if (d.dtype == VK_F32 || d.R != 3 || d.S != 3 || d.stride != 1 || d.pad != 1 || d.src0.up || d.src0.C != d.K || (d.K != 16 && d.K != 32)) return VK_OK;
+  vk_conv_desc d = conv_desc(h, c, to_src(bn_act(h, into), up), null_src());
+  if (d.dtype == VK_F32 || d.R != 3 || d.S != 3 || d.stride != 1 || d.pad != 1) return VK_OK;
+  if (up ? (d.src0.C != 32 || d.K != 16 || ((d.H | d.W) & 1)) : (d.src0.C != d.K || (d.K != 16 && d.K != 32))) return VK_OK;
   static const int maxc = getenv("VK_BN_APPLY_FUSED_MAXC") ? atoi(getenv("VK_BN_APPLY_FUSED_MAXC")) : VK_BN_APPLY_FUSED_MAXC_DEFAULT;
   if (!frozen(h, b) && c.K <= maxc) return VK_OK;            // that switch derives the coefficients inside the apply kernel
   // the coefficient launch of bn_bwd_phase2 (frozen statistics: (a, 0, 0) is in b.coef since the forward)
@@ -1527,7 +1529,7 @@ int backward_decoder(vk_unet* h, int i, hipStream_t st) {
   int onepass = 0;
   if (h->g_prereduced[d.conv2] && into1 && trains(h, c2.w_t) && h->cfg.dtype != VK_F32 && !h->side && !on_1x1(c2) && !getenv("VK_NO_ONEPASS") &&
       !getenv("VK_NO_BNR_FUSION"))
-    RET_IF(conv_bwd_onepass(h, c2, c1, &onepass, st));
+    RET_IF(conv_bwd_onepass(h, c2, c1, 0, &onepass, st));
   if (onepass == 1) {
     fused1 = true;
   } else {
@@ -1537,8 +1539,18 @@ int backward_decoder(vk_unet* h, int i, hipStream_t st) {
   }
   if (i > 0) h->g_prereduced[h->decs[i - 1].conv2] = 0;
   if (!into1) return VK_OK;
-  // conv1 unit
-  RET_IF(bn_relu_bwd_inplace(h, c1, fused1, st));
+  // conv1 unit.  A block without skip source behind another block (dec4.conv1) takes the upsampled form of the one-pass kernel:
+  // apply, pooled data gradient with the reduce of the previous block's conv2, and weight gradient at once.  VK_NO_ONEPASS_UP=1 (read
+  // per launch) switches this route alone off.
+  int onepass1 = 0;
+  if (fused1 && i > 0 && !d.Cskip && trains(h, c1.w_t) && need_from(h, c1.rank + 1) && h->cfg.dtype != VK_F32 && !h->side && !on_1x1(c1) &&
+      !getenv("VK_NO_ONEPASS") && !getenv("VK_NO_ONEPASS_UP") && !getenv("VK_NO_BNR_FUSION"))
+    RET_IF(conv_bwd_onepass(h, c1, h->convs[h->decs[i - 1].conv2], 1, &onepass1, st));
+  if (onepass1 == 1) {
+    h->g_prereduced[h->decs[i - 1].conv2] = 1;
+    return VK_OK;
+  }
+  if (onepass1 == 0) RET_IF(bn_relu_bwd_inplace(h, c1, fused1, st));
   // data gradient with the nearest-x2 upsample backward fused into its epilogue (the full-resolution d_up never exists)
   // and, for i > 0, the BN+ReLU backward reduce of the previous decoder block's conv2;
   // shapes the tile kernels do not cover fall back to dgrad + a separate 2x2-sum pass

@@ -33,6 +33,8 @@
  *   vk_geom_minarearect ....................... postprocess_minarearect_multi      ui_infer_rectangle.py:291-381
  *   vk_geom_quadrilateral ..................... postprocess_minarearect_multi + robust_quadrilateral_from_contour  ui_infer_quadrilateral.py:262-530
  *   vk_letterbox_u8 / _mask_u8 / vk_augment_batch  VickersDataset.__getitem__ + albumentations pipeline  train.py:67-113, 173-200
+ *   vk_patch_index / vk_patch_batch ........... random S x S training patches of the full-resolution images (no counterpart: the
+ *                                               reference trains on letterboxed images only)
  *
  * Conventions
  *   - plain pointers and sizes only; no C++/torch types cross this boundary.
@@ -442,6 +444,56 @@ int vk_letterbox_mask_u8(const vk_letterbox_desc* d, const uint8_t* mask_hw, uin
 int vk_augment_batch(int n, int size, int n_items, const uint8_t* images_rgb, const uint8_t* masks, const int* index_dev,
                      const vk_aug_params* params_host, void* params_dev, const int* color_tables, void* workspace,
                      size_t workspace_bytes, float* x, float* y, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Native-resolution patch training: the training-side half of the sliding-window inference above.  The images stay
+ * on the device at their OWN size — uint8 BGR [h][w][3], concatenated in one store, every item starting on a multiple of 4 bytes and
+ * padded to one; masks [h][w] in a second store (any non-zero byte is foreground) — and every step cuts n random S x S patches out of
+ * them into the uint8 RGB [n][S][S][3] / mask {0,1} [n][S][S] buffers that vk_augment_batch then reads with index = 0..n-1.
+ * Every byte offset is 64-bit: the store may exceed 2^31 bytes.
+ *
+ * Origin of a sample (int32 (y0, x0), the patch's top-left corner in source pixels).  With k >= 0 and a non-empty mask: k is clamped
+ * to count - 1, (py, px) is the k-th foreground pixel of the item in raster order, and (y0, x0) = (py - oy, px - ox); otherwise
+ * (y0, x0) = (oy, ox).  Then per axis of length L: L >= S: o = min(max(o, 0), L - S); L < S: o = -((S - L) / 2) (integer division: the
+ * image centred in the patch, as PadIfNeeded centres it).
+ * Crop, float32 without fused multiply-add, for output pixel (y, x): c = S*0.5f - 0.5f, dx = x - c, dy = y - c, cx = (float)x0 + c,
+ * cy = (float)y0 + c, u = ((cos*dx - sin*dy) * zoom) + cx, v = ((sin*dx + cos*dy) * zoom) + cy.  Image: the four bilinear taps at
+ * (floor(v), floor(u)) combined as vk_augment_batch's rotation combines them (top = t00*(1-wx) + t01*wx, bot likewise,
+ * top*(1-wy) + bot*wy), taps outside the IMAGE read 0, rintf, clamp to 0..255, BGR -> RGB.  Mask: nearest, at
+ * (floor(v + 0.5f), floor(u + 0.5f)), 0 outside.  A sample with cos == 1, sin == 0, zoom == 1 is copied row by row instead; the bits are
+ * the same (every coordinate is then an exact integer or half-integer below 2^23); VK_PATCH_FORCE_GENERAL sends it down the general path.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+  int64_t img_off;      /* byte offset of the item's BGR pixels in the image store, a multiple of 4 */
+  int64_t msk_off;      /* byte offset of its mask in the mask store, a multiple of 4 */
+  int h, w;             /* 1..16384 */
+  int64_t row_off;      /* index of its first entry in the row table (h entries) */
+} vk_patch_item;
+
+typedef struct {
+  int item;             /* 0..n_items-1 */
+  int k;                /* foreground rank, or < 0: (oy, ox) is the origin itself */
+  int oy, ox;           /* k >= 0: where in the patch the chosen pixel lands, 0..S-1; k < 0: the origin (before clamping); 0..16384 */
+  float zoom;           /* source pixels per output pixel, 0.25..4 */
+  float cos_a, sin_a;   /* rotation about the patch centre, as vk_aug_params */
+  int reserved;         /* 0 */
+} vk_patch_params;
+
+#define VK_PATCH_FORCE_GENERAL 1
+
+/* Once per dataset: checks items_host[n_items] (sizes, alignment, every item — its image padded to whole dwords — inside images_bytes /
+ * masks_bytes / rowcum_len; VK_ERR_ARG before anything touches the stream), copies the table to items_dev (device,
+ * n_items * sizeof(vk_patch_item)) and fills rowcum (device, int32): rowcum[row_off + r] = foreground pixels of rows 0..r of the item,
+ * so rowcum[row_off + h - 1] is its total.  Integer sums only: deterministic.  masks must be 4-byte aligned. */
+int vk_patch_index(int n_items, const vk_patch_item* items_host, void* items_dev, size_t images_bytes, const uint8_t* masks,
+                   size_t masks_bytes, int32_t* rowcum, size_t rowcum_len, void* stream);
+/* Per step: checks on the host (n 1..65535, size 1..16384, every item in range, zoom in [0.25, 4], |cos^2 + sin^2 - 1| < 1e-3, offsets,
+ * flags, no null buffer, images 4-byte aligned; VK_ERR_ARG before anything touches the stream), copies params_host[n] to params_dev
+ * (device scratch, n * sizeof), then writes origins int32 [n][2] (device; readable by the caller), patches_rgb and patches_mask.
+ * items_dev and rowcum are those vk_patch_index filled. */
+int vk_patch_batch(int n, int size, int n_items, const void* items_dev, const uint8_t* images, const uint8_t* masks, const int32_t* rowcum,
+                   const vk_patch_params* params_host, void* params_dev, int flags, int32_t* origins, uint8_t* patches_rgb,
+                   uint8_t* patches_mask, void* stream);
 
 /* NCHW fp32 [N][3][H][W] -> NHWC4 `dtype` */
 int vk_input_transform(vk_dtype dtype, int N, int H, int W, const float* x, void* x4, void* stream);

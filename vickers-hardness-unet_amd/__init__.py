@@ -10,8 +10,9 @@ Import by string (the directory name carries hyphens)::
     optimizer = vk.adamw_for(model, lr=5e-5, weight_decay=1e-4)
 
 Everything heavy runs in libvkunet.so (hand-written HIP); there is no CPU fallback."""
-from . import _lib, augment, encoders, geometry, losses, lovasz, multiclass, parallel, prepost, seglosses, segmetrics, synthetic, tiling  # noqa: F401
+from . import _lib, augment, encoders, geometry, losses, lovasz, multiclass, parallel, patches, prepost, seglosses, segmetrics, synthetic, tiling  # noqa: F401
 from .augment import AugmentSampler, DeviceDataset  # noqa: F401
+from .patches import PatchDataset, PatchSampler  # noqa: F401
 from .geometry import (postprocess_minarearect_batch, postprocess_minarearect_multi, postprocess_quadrilateral_batch,  # noqa: F401
                        postprocess_quadrilateral_multi)
 from ._lib import VkError, build, lib  # noqa: F401
@@ -25,5 +26,5 @@ from .unet import Unet, build_model  # noqa: F401
 
 __all__ = ["Unet", "build_model", "DiceLoss", "BCEDiceLoss", "multiclass", "encoders", "FusedAdamW", "GradScaler", "adamw_for", "clip_grad_norm_", "finetune_groups", "GradientReducer",
            "make_data_parallel", "broadcast_model", "all_reduce_scalars", "dice_coef", "iou_coef", "seg_metrics", "seg_metrics_device", "synthetic_batch", "seed_everything",
-           "VkError", "build", "lib", "losses", "lovasz", "seglosses", "segmetrics", "synthetic", "parallel", "prepost", "Segmenter", "predict_mask", "predict_mask_tiled", "tiling", "geometry", "augment", "AugmentSampler", "DeviceDataset",
+           "VkError", "build", "lib", "losses", "lovasz", "seglosses", "segmetrics", "synthetic", "parallel", "prepost", "Segmenter", "predict_mask", "predict_mask_tiled", "tiling", "geometry", "augment", "AugmentSampler", "DeviceDataset", "patches", "PatchDataset", "PatchSampler",
            "postprocess_minarearect_multi", "postprocess_minarearect_batch", "postprocess_quadrilateral_multi", "postprocess_quadrilateral_batch"]

@@ -20,6 +20,7 @@ VK_ADAMW_MAX_GROUPS = 8
 VK_NORM_L2, VK_NORM_INF = 0, 1
 VK_TILE_MAX_ORIGINS, VK_TILE_MAX_SIDE = 64, 4096
 VK_BLEND_PROB, VK_BLEND_LOGIT = 0, 1
+VK_PATCH_FORCE_GENERAL = 1
 
 
 class VkError(RuntimeError):
@@ -74,6 +75,15 @@ class vk_aug_params(C.Structure):
     _fields_ = [("d4", C.c_int), ("rotate", C.c_int), ("cos_a", C.c_float), ("sin_a", C.c_float), ("photo", C.c_int),
                 ("alpha", C.c_float), ("beta", C.c_float), ("blur_ksize", C.c_int), ("noise_scale", C.c_float),
                 ("noise_seed", C.c_uint32), ("clahe_limit", C.c_int)]
+
+
+class vk_patch_item(C.Structure):
+    _fields_ = [("img_off", C.c_int64), ("msk_off", C.c_int64), ("h", C.c_int), ("w", C.c_int), ("row_off", C.c_int64)]
+
+
+class vk_patch_params(C.Structure):
+    _fields_ = [("item", C.c_int), ("k", C.c_int), ("oy", C.c_int), ("ox", C.c_int), ("zoom", C.c_float), ("cos_a", C.c_float),
+                ("sin_a", C.c_float), ("reserved", C.c_int)]
 
 
 class vk_seg_loss_cfg(C.Structure):
@@ -154,6 +164,8 @@ SIGNATURES = {
     "vk_letterbox_mask_u8": (ci, [P(vk_letterbox_desc), vp, vp, vp]),
     "vk_augment_workspace_bytes": (C.c_size_t, [ci, ci]),
     "vk_augment_batch": (ci, [ci, ci, ci, vp, vp, vp, P(vk_aug_params), vp, vp, vp, C.c_size_t, vp, vp, vp]),
+    "vk_patch_index": (ci, [ci, P(vk_patch_item), vp, sz, vp, sz, vp, sz, vp]),
+    "vk_patch_batch": (ci, [ci, ci, ci, vp, vp, vp, vp, P(vk_patch_params), vp, ci, vp, vp, vp, vp]),
     "vk_input_transform": (ci, [ci, ci, ci, ci, vp, vp, vp]),
     "vk_bn_finalize": (ci, [ci, ci, vp, cd, vp, vp, vp, vp, cf, cf, vp, vp, vp, vp, vp]),
     "vk_bn_relu_maxpool": (ci, [ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]),

@@ -14,6 +14,8 @@
  *   vk_unet_set_input_grad .................... x.requires_grad_() (x.grad: saliency maps)
  *   vk_seg_metrics ............................ dice_coef / iou_coef (validate) train.py:230-281, 518-522
  *   vk_seg_metrics_multi ...................... the same per class for Unet(classes=C): counts tp/fp/fn/tn, Dice / IoU per class
+ *   vk_sweep_hist / vk_sweep_curves ........... validate's Dice / IoU at every threshold of a grid from one pass (the reference's GUIs
+ *                                               hand-pick 0.50 and 0.45), plus the precision-recall and ROC curves
  *   vk_comm_* / vk_allreduce_bucket ........... (no reference counterpart: the 8-GPU data-parallel exchange)
  *   vk_adamw_step ............................. optimizer.step()/zero_grad   train.py:428, 449 (606)
  *   vk_amp_check_inf / vk_amp_unscale_check /
@@ -722,6 +724,55 @@ size_t vk_seg_metrics_multi_workspace_bytes(int n_images, int C);
 int vk_seg_metrics_multi(int mode, int n_images, int C, size_t per_image, const float* logits, const void* target, int from_logits,
                          float threshold, float eps, void* workspace, size_t workspace_bytes, int64_t* stats, float* out,
                          int* bad_labels, void* stream);
+
+/* Threshold sweep (sweep.hip): the counts of vk_seg_metrics / vk_seg_metrics_multi (multilabel) for EVERY threshold of a grid from one
+ * pass over prediction and target, and the curves that follow from them.
+ *
+ * vk_sweep_hist.  A plane is one (image, class) map of per_plane elements (1 <= per_plane < 2^31); plane p starts plane_stride elements
+ * after plane p - 1 in both tensors (0 = per_plane; a larger stride feeds a part of every plane).  pred fp32: probabilities or scores,
+ * or logits when from_logits != 0 (then pv = 1 / (1 + expf(-x)), vk_seg_metrics' expression).  target fp32, or uint8 when target_u8 != 0:
+ * 1 is positive, 0 negative, a value equal to ignore_index (when has_ignore != 0) is skipped, any other value is skipped and counted
+ * in *bad (device int).  thr_host: K thresholds on the HOST, 1 <= K <= 1024, finite and strictly ascending (checked before anything
+ * is launched); thr_dev: the same K floats in device memory, which the kernel reads (garbage there gives garbage counts, never an
+ * access outside a buffer).  hist (device int32 [n_planes][2][K + 1]): hist[p][t][b] = number of valid elements of plane p with target t
+ * and bin b = #{k : pv > thr[k]} (strict; NaN compares false and lands in bin 0, +inf in bin K).  accumulate == 0 zeroes hist and *bad
+ * first, accumulate != 0 adds to them.  Integer atomics only: bit-reproducible.  For threshold k: P = sum over b > k of both rows,
+ * I = sum over b > k of row 1, T = sum of row 1 are vk_seg_metrics' sums at threshold thr[k].
+ * 16-byte loads of the prediction (and of an fp32 target; 4-byte loads of a uint8 one) when the pointers are aligned to them and
+ * per_plane and plane_stride are multiples of 4; otherwise a scalar path.
+ *
+ * vk_sweep_curves.  hist (device int32 [N][C][2][K + 1]) -> every output listed in vk_sweep_layout, written at its byte offset into
+ * `out` (device, 8-byte aligned, at least total_bytes = vk_sweep_curves_out_bytes):
+ *   stats       int64 [K][4][N][C] {tp, fp, fn, tn} and per_image fp32 [K][N][C][2] {dice, iou}: row k is what vk_seg_metrics_multi
+ *               (multilabel) writes at threshold thr[k], same expressions, same order;
+ *   dice, iou   fp32 [K][C]: the class's fp64 mean over the images rounded once (worker j sums images j, j + 64, ...; the 64 partials
+ *               are added in j order); mean_dice, mean_iou fp32 [K]: the fp64 mean of the rounded class scores, rounded once;
+ *   micro_stats int64 [4][K][C]: the counts pooled over the images; micro fp64 [5][K][C] = precision tp / (tp + fp), recall
+ *               tp / (tp + fn), f1 2 tp / (2 tp + fp + fn), iou tp / (tp + fp + fn), fpr fp / (fp + tn); a ratio with a zero denominator
+ *               is 1, the fpr 0;
+ *   ap, auc     fp64 [C]: AP = sum_k (recall_k - recall_{k+1}) precision_k with recall_K = 0; ROC-AUC by the trapezoid rule over
+ *               (1, 1), (fpr_k, recall_k) for k ascending, (0, 0).  Both see only the grid's operating points;
+ *   best_dice, best_iou, best_f1 int32 [C]: the lowest k of the best dice[k][c], iou[k][c], micro f1; best_mean int32 [2]: the same
+ *               for mean_dice and mean_iou.
+ * group (optional, device int32 [N], with n_groups = G in [1, N]) names the validation batch of every image; an image whose value is
+ * outside [0, G) belongs to no batch.  Then also group_dice, group_iou fp32 [G][K][C], group_mean_dice, group_mean_iou fp32 [G][K]: the
+ * same means over the group's images, numbered from 0 in ascending image index (one vk_seg_metrics call over that batch), and
+ * epoch_dice, epoch_iou fp64 [K][C], epoch_mean_dice, epoch_mean_iou fp64 [K]: (sum over g ascending of (double) score_g) / G, the
+ * reference's validate (train.py:518-529).  workspace: workspace_bytes of the layout, 8-byte aligned device scratch (none without
+ * groups).  N in [1, 65535], C in [1, 16], K in [1, 1024].  Neither call synchronises; contraction is off, every operation is IEEE in
+ * a fixed order. */
+typedef struct vk_sweep_layout {
+  size_t stats, per_image, dice, iou, mean_dice, mean_iou, micro_stats, micro, ap, auc, best_dice, best_iou, best_f1, best_mean;
+  size_t group_dice, group_iou, group_mean_dice, group_mean_iou, epoch_dice, epoch_iou, epoch_mean_dice, epoch_mean_iou;
+  size_t total_bytes, workspace_bytes;
+} vk_sweep_layout;
+int vk_sweep_hist(int n_planes, size_t per_plane, size_t plane_stride, const float* pred, const void* target, int target_u8,
+                  int from_logits, int has_ignore, int ignore_index, int K, const float* thr_host, const float* thr_dev, int accumulate,
+                  int32_t* hist, int* bad, void* stream);
+int vk_sweep_curves_layout(int n_images, int C, int K, int n_groups, vk_sweep_layout* layout);
+size_t vk_sweep_curves_out_bytes(int n_images, int C, int K, int n_groups);     /* 0 when a size is out of range */
+int vk_sweep_curves(int n_images, int C, int K, const int32_t* hist, const int32_t* group, int n_groups, float eps, void* workspace,
+                    size_t workspace_bytes, void* out, size_t out_bytes, void* stream);
 
 /* AdamW (decoupled decay) over a flat fp32 parameter buffer; optionally emits the 16-bit working copy.
  * inv_scale multiplies the gradient first (GradScaler unscale / data-parallel averaging).

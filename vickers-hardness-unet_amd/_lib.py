@@ -104,6 +104,15 @@ class vk_lovasz_cfg(C.Structure):
                 ("ignore_index", C.c_int32)]
 
 
+SWEEP_FIELDS = ("stats", "per_image", "dice", "iou", "mean_dice", "mean_iou", "micro_stats", "micro", "ap", "auc", "best_dice", "best_iou",
+                "best_f1", "best_mean", "group_dice", "group_iou", "group_mean_dice", "group_mean_iou", "epoch_dice", "epoch_iou",
+                "epoch_mean_dice", "epoch_mean_iou")
+
+
+class vk_sweep_layout(C.Structure):
+    _fields_ = [(f, C.c_size_t) for f in SWEEP_FIELDS + ("total_bytes", "workspace_bytes")]
+
+
 class vk_adamw_group(C.Structure):
     _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float)]
 
@@ -200,6 +209,10 @@ SIGNATURES = {
     "vk_seg_metrics": (ci, [ci, sz, vp, vp, ci, cf, cf, vp, sz, vp, vp]),
     "vk_seg_metrics_multi_workspace_bytes": (sz, [ci, ci]),
     "vk_seg_metrics_multi": (ci, [ci, ci, ci, sz, vp, vp, ci, cf, cf, vp, sz, vp, vp, vp, vp]),
+    "vk_sweep_hist": (ci, [ci, sz, sz, vp, vp, ci, ci, ci, ci, ci, vp, vp, ci, vp, vp, vp]),
+    "vk_sweep_curves_layout": (ci, [ci, ci, ci, ci, P(vk_sweep_layout)]),
+    "vk_sweep_curves_out_bytes": (sz, [ci, ci, ci, ci]),
+    "vk_sweep_curves": (ci, [ci, ci, ci, vp, vp, ci, cf, vp, sz, vp, sz, vp]),
     "vk_adamw_step": (ci, [sz, vp, vp, vp, vp, cf, cf, cf, cf, cf, ci, cf, vp, vp, ci, vp]),
     "vk_amp_check_inf": (ci, [sz, vp, vp, vp]),
     "vk_amp_unscale_check": (ci, [sz, vp, vp, vp, vp]),

@@ -408,6 +408,20 @@ typedef struct {
 int vk_geom_quadrilateral(const vk_geom_desc* d, int fit_outset_px, int batch, const float* prob, uint8_t* clean, vk_geom_quad* dets,
                           int* counts, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The label map of the latest geometry call, as slots of its detection list.
+ *
+ * Contract: after vk_geom_minarearect or vk_geom_quadrilateral returns, the workspace holds the flattened label image and the slot of
+ * every component's representative, and neither call writes them after its labelling front end.  They stay valid until the next call
+ * that is given the same workspace.  This call reads the workspace exactly as that latest call left it: the descriptor, `batch` and
+ * the stream must be the same as in that call (the same stream orders it after the kernels that fill the workspace).  It writes
+ * nothing but `slots`, device int32 [batch][h][w]:
+ *   s >= 0   the pixel belongs to the component in slot s of that map's detection list (slots are in label order, the order in which
+ *            `dets` is filled), so slot s covers exactly dets[s].area pixels;
+ *   -1       background, or a component with area < min_area (absent from `clean`);
+ *   -2       a kept component beyond max_components: it shows in `clean` and in `counts` but has no record.
+ * A workspace that no geometry call has filled gives a meaningless map, never an access outside the buffers. */
+int vk_geom_slot_map(const vk_geom_desc* d, int batch, const void* workspace, size_t workspace_bytes, int32_t* slots, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Training-time augmentation on the device: VickersDataset.__getitem__ (train.py:173-200) with the
  * albumentations pipeline of train.py:67-113.  The dataset is letterboxed ONCE into uint8 tensors that stay in HBM
@@ -773,6 +787,49 @@ int vk_sweep_curves_layout(int n_images, int C, int K, int n_groups, vk_sweep_la
 size_t vk_sweep_curves_out_bytes(int n_images, int C, int K, int n_groups);     /* 0 when a size is out of range */
 int vk_sweep_curves(int n_images, int C, int K, const int32_t* hist, const int32_t* group, int n_groups, float eps, void* workspace,
                     size_t workspace_bytes, void* out, size_t out_bytes, void* stream);
+
+/* Object-level validation (instances.hip): which indentations were found, and how far off are their diagonals.  The object-level
+ * companion of the pixel counts above: integer counts and IEEE operations in a fixed order, contraction off, no call synchronises.
+ *
+ * vk_inst_contingency.  pred_slots, gt_slots: device int32 [batch][h][w], two outputs of vk_geom_slot_map (h * w < 2^30, batch in
+ * 1..65535).  table: device int32 [batch][Mp + 1][Mg + 1], zeroed by the call; Mp, Mg in 1..256.  Index 0 means "none", index 1 + s
+ * means slot s; a slot value outside [0, M) (-1, -2, any other negative value, any value >= M) counts as none and never addresses
+ * the table.  table[b][i][j] = pixels of map b with pred index i and GT index j; every table sums to h * w, [0][0] included (that cell
+ * is derived as h * w minus the rest).  Integer atomics only: bit-reproducible.  16-byte loads when both maps are 16-byte aligned
+ * and w is a multiple of 4, otherwise a scalar path.
+ *
+ * vk_inst_match.  table as above.  n_pred, n_gt: device int32 [batch], the `counts` of the two geometry calls; the call uses
+ * min(count, M) slots (a negative count as 0) and flags the image when count > M.  iou_thresholds: K doubles on the HOST, 1 <= K <= 16,
+ * finite, strictly ascending, in [0.5, 1), checked before anything is launched and passed by value.  diag_pred, diag_gt (optional,
+ * used only when both are given): the float64 d_mean of slot s of image b is at (char*)diag + ((size_t)b * M + s) * stride, stride in
+ * bytes and a multiple of 8, so records of vk_geom_det or vk_geom_quad are read in place.
+ *   Ap(i) = sum of row i, Ag(j) = sum of column j, each with its "none" cell; I = table[i][j]; U = Ap + Ag - I.
+ *   Pred slot s < n_pred_used and GT slot t < n_gt_used are a CANDIDATE iff 3 I > Ap + Ag in int64: IoU > 1/2 exactly, hence at most
+ *   one candidate per pred slot and per GT slot, no ties and no greedy order.  iou = (double)I / (double)U.  The pair is MATCHED at
+ *   threshold k iff it is a candidate and iou > thr[k] (strict: the panoptic-quality convention).
+ * Per pred slot, [batch][Mp]: pair_gt int32 (the candidate's GT slot or -1), pair_iou fp64 (0 without a candidate), pair_derr fp64
+ * (dp - dg; 0 without a candidate or without diagonals).  Slots at or above n_pred_used get -1, 0, 0.
+ * per_image [batch][K] and totals [K] are vk_inst_stats records.  Per image and threshold: tp, fp = n_pred_used - tp,
+ * fn = n_gt_used - tp, and over the matched pairs in ascending pred slot, each sum sequential in fp64: sum_iou, sum_abs_d = sum |dp - dg|,
+ * max_abs_d, and over those of them with dg > 0 and dp > 0 (their number is n_rel): sum_rel_d = sum |dp - dg| / dg,
+ * sum_signed_rel_d = sum (dp - dg) / dg, sum_hv_rel = sum ((dg / dp) * (dg / dp) - 1.0), the relative error of a hardness that goes as
+ * 1 / d^2.  Without diagonals these are 0.  The same for every threshold of an image: n_pred_used, n_gt_used, n_split (GT slots
+ * that two or more pred slots touch with I > 0), n_merge (pred slots that two or more GT slots touch), overflow_pred / overflow_gt
+ * (1 when count > M), n_images = 1.
+ * totals[k] starts from zero, or from its contents when accumulate != 0; then image 0 is added, then image 1, and so on (max_abs_d by
+ * maximum): an epoch's totals are one flat sequence over its images and their bits do not depend on how it was cut into batches.
+ * One call is two launches: one workgroup per image, then the pass over the images. */
+typedef struct vk_inst_stats {
+  int64_t tp, fp, fn, n_rel;
+  int64_t n_pred_used, n_gt_used, n_split, n_merge, overflow_pred, overflow_gt, n_images;
+  double sum_iou, sum_abs_d, sum_rel_d, sum_signed_rel_d, sum_hv_rel, max_abs_d;
+} vk_inst_stats;
+int vk_inst_contingency(int batch, int h, int w, const int32_t* pred_slots, const int32_t* gt_slots, int Mp, int Mg, int32_t* table,
+                        void* stream);
+int vk_inst_match(int batch, int Mp, int Mg, const int32_t* table, const int32_t* n_pred, const int32_t* n_gt, int K,
+                  const double* iou_thresholds, const void* diag_pred, size_t diag_pred_stride, const void* diag_gt,
+                  size_t diag_gt_stride, int32_t* pair_gt, double* pair_iou, double* pair_derr, vk_inst_stats* per_image,
+                  vk_inst_stats* totals, int accumulate, void* stream);
 
 /* AdamW (decoupled decay) over a flat fp32 parameter buffer; optionally emits the 16-bit working copy.
  * inv_scale multiplies the gradient first (GradScaler unscale / data-parallel averaging).

@@ -113,6 +113,14 @@ class vk_sweep_layout(C.Structure):
     _fields_ = [(f, C.c_size_t) for f in SWEEP_FIELDS + ("total_bytes", "workspace_bytes")]
 
 
+INST_INT_FIELDS = ("tp", "fp", "fn", "n_rel", "n_pred_used", "n_gt_used", "n_split", "n_merge", "overflow_pred", "overflow_gt", "n_images")
+INST_FLOAT_FIELDS = ("sum_iou", "sum_abs_d", "sum_rel_d", "sum_signed_rel_d", "sum_hv_rel", "max_abs_d")
+
+
+class vk_inst_stats(C.Structure):
+    _fields_ = [(f, C.c_int64) for f in INST_INT_FIELDS] + [(f, C.c_double) for f in INST_FLOAT_FIELDS]
+
+
 class vk_adamw_group(C.Structure):
     _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float)]
 
@@ -169,6 +177,7 @@ SIGNATURES = {
     "vk_geom_workspace_bytes": (i64, [P(vk_geom_desc), ci]),
     "vk_geom_minarearect": (ci, [P(vk_geom_desc), ci, vp, vp, vp, vp, vp, sz, vp]),
     "vk_geom_quadrilateral": (ci, [P(vk_geom_desc), ci, ci, vp, vp, vp, vp, vp, sz, vp]),
+    "vk_geom_slot_map": (ci, [P(vk_geom_desc), ci, vp, sz, vp, vp]),
     "vk_letterbox_u8": (ci, [P(vk_letterbox_desc), vp, vp, vp]),
     "vk_letterbox_mask_u8": (ci, [P(vk_letterbox_desc), vp, vp, vp]),
     "vk_augment_workspace_bytes": (C.c_size_t, [ci, ci]),
@@ -213,6 +222,8 @@ SIGNATURES = {
     "vk_sweep_curves_layout": (ci, [ci, ci, ci, ci, P(vk_sweep_layout)]),
     "vk_sweep_curves_out_bytes": (sz, [ci, ci, ci, ci]),
     "vk_sweep_curves": (ci, [ci, ci, ci, vp, vp, ci, cf, vp, sz, vp, sz, vp]),
+    "vk_inst_contingency": (ci, [ci, ci, ci, vp, vp, ci, ci, vp, vp]),
+    "vk_inst_match": (ci, [ci, ci, ci, vp, vp, vp, ci, vp, vp, sz, vp, sz, vp, vp, vp, vp, vp, ci, vp]),
     "vk_adamw_step": (ci, [sz, vp, vp, vp, vp, cf, cf, cf, cf, cf, ci, cf, vp, vp, ci, vp]),
     "vk_amp_check_inf": (ci, [sz, vp, vp, vp]),
     "vk_amp_unscale_check": (ci, [sz, vp, vp, vp, vp]),

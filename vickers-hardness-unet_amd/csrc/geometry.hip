@@ -1152,3 +1152,43 @@ extern "C" int vk_geom_quadrilateral(const vk_geom_desc* d, int fit_outset_px, i
   VK_CHECK_HIP(hipGetLastError());
   return VK_OK;
 }
+
+// ---------------------------------------------------------------------------------------------- the slot map
+// What k_geom_clean_rows looks up per pixel, as an output: the slot of the pixel's component in the detection list.  L (flattened:
+// every foreground pixel holds its representative) and the slot-per-representative array that k_geom_assign left in `area` are not
+// written by anything after geom_front, so this reads the workspace of the latest call as it is.  A label outside the map (a
+// workspace that no call has filled) reads as background.
+namespace vk {
+__global__ __launch_bounds__(256) void k_geom_slot_map(size_t n_img, int batch, const int* __restrict__ Lb, const int* __restrict__ slot_b,
+                                                       int* __restrict__ slots) {
+  const size_t total = n_img * batch;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int lab = Lb[i];
+    int s = -1;
+    if (lab >= 0 && (size_t)lab < n_img) {
+      s = slot_b[(i / n_img) * n_img + lab];
+      if (s < -2) s = -1;
+    }
+    slots[i] = s;
+  }
+}
+}  // namespace vk
+
+extern "C" int vk_geom_slot_map(const vk_geom_desc* d, int batch, const void* workspace, size_t workspace_bytes, int32_t* slots,
+                                void* stream) {
+  int rc = geom_check(d, batch, "vk_geom_slot_map");
+  if (rc != VK_OK) return rc;
+  VK_CHECK_ARG(workspace && slots, "vk_geom_slot_map: null buffer");
+  const GeomLayout g = geom_layout(d, batch);
+  VK_CHECK_ARG(workspace_bytes >= g.total, "vk_geom_slot_map: workspace too small (%zu < %zu)", workspace_bytes, g.total);
+  VK_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "vk_geom_slot_map: workspace must be 256-byte aligned");
+  VK_CHECK_ARG(((uintptr_t)slots & 3) == 0, "vk_geom_slot_map: misaligned buffer");
+  hipStream_t st = (hipStream_t)stream;
+  const char* ws = (const char*)workspace;
+  const size_t n = (size_t)d->h * d->w;
+  vkh::ProfScope ps("geom_slot_map", st, 0.0, (double)batch * (double)n * 12.0);
+  hipLaunchKernelGGL(k_geom_slot_map, dim3((unsigned)std::min<size_t>((n * batch + 255) / 256, 8192)), dim3(256), 0, st, n, batch,
+                     (const int*)(ws + g.L), (const int*)(ws + g.area), slots);
+  VK_CHECK_HIP(hipGetLastError());
+  return VK_OK;
+}

@@ -292,6 +292,7 @@ def test_loss_and_backward_equals_autograd(classes, dtype):
     x, tgt = x.to(dev()), tgt.to(dev())
     m = _model(classes)
     sd = copy.deepcopy(m.state_dict())
+    ptrs = set()                       # where the fused steps put their results: one buffer of the plan, not one per call
 
     def autograd(scale=1.0):
         m.load_state_dict(sd)
@@ -309,6 +310,7 @@ def test_loss_and_backward_equals_autograd(classes, dtype):
         m.zero_grad(set_to_none=True)
         out = m.loss_and_backward(x, tgt, grad_scale=scale, dtype=dtype, loss=S)
         torch.cuda.synchronize()
+        ptrs.add(out.data_ptr())
         return out.clone(), m.flat_grads.detach().clone()
 
     l_a, g_a = autograd()
@@ -317,11 +319,13 @@ def test_loss_and_backward_equals_autograd(classes, dtype):
     assert abs(l_f[0].item() - l_a.item()) <= 1e-5 * abs(l_a.item())
     assert ((g_f - g_a).norm() / g_a.norm()).item() <= 1e-5
     assert torch.equal(S.last_components, l_f) and l_f[7].item() > 0 and l_f[1].item() > 0
+    assert tuple(m.last_logits.shape) == (x.shape[0], classes) + tuple(x.shape[2:])
     _, g_s = fused(scale=256.0)
     assert ((g_s - 256.0 * g_f).norm() / (256.0 * g_f).norm()).item() <= 1e-5
     # two seeded steps are bit-identical
     l_2, g_2 = fused()
     assert torch.equal(l_2, l_f) and torch.equal(g_2, g_f)
+    assert len(ptrs) == 1
     # a plain vk.seglosses sum keeps its 6-entry result
     m.load_state_dict(sd)
     m.zero_grad(set_to_none=True)

@@ -291,6 +291,7 @@ def test_loss_and_backward_equals_autograd(mode, dtype):
     fused = vk.multiclass.BCEDiceLoss(mode="multilabel") if mode == "multilabel" else vk.multiclass.CEDiceLoss()
     m.train()
     sd = copy.deepcopy(m.state_dict())
+    ptrs = set()                       # where the fused steps put their results: one buffer of the plan, not one per call
 
     def autograd(loss_fn, scale=1.0):
         m.load_state_dict(sd)
@@ -308,11 +309,13 @@ def test_loss_and_backward_equals_autograd(mode, dtype):
         m.zero_grad(set_to_none=True)
         out = m.loss_and_backward(x, tgt, grad_scale=scale, dtype=dtype, mode=mode)
         torch.cuda.synchronize()
+        ptrs.add(out.data_ptr())
         return out.clone(), _flat_grads(m)
 
     l_vk, g_vk = autograd(fused)
     l_f, g_f = fused_step()
     assert torch.equal(l_f[0], l_vk) and torch.equal(g_f, g_vk)            # same kernels, same bits
+    assert tuple(m.last_logits.shape) == (2, Cc, 64, 64)
     l_t, g_t = autograd(lambda lg, tg: _torch_loss(mode, lg, tg if mode == "multilabel" else None,
                                                    tg if mode == "multiclass" else None, vk.multiclass.DiceLoss(mode=mode)))
     assert abs(l_t.item() - l_f[0].item()) <= 1e-5 * abs(l_f[0].item())
@@ -325,6 +328,7 @@ def test_loss_and_backward_equals_autograd(mode, dtype):
     _, g_as = autograd(fused, scale=256.0)
     assert torch.equal(g_s, g_as)
     assert ((g_s - 256.0 * g_f).norm() / (256.0 * g_f).norm()).item() <= 1e-5
+    assert len(ptrs) == 1
     with pytest.raises(ValueError, match="multilabel"):
         m.loss_and_backward(x, tgt, dtype=dtype)                           # classes > 1 and no mode
 

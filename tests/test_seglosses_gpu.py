@@ -237,6 +237,7 @@ def test_loss_and_backward_equals_autograd(classes, dtype):
     x, tgt = x.to(dev()), tgt.to(dev())
     m = _model(classes)
     sd = copy.deepcopy(m.state_dict())
+    ptrs = set()                       # where the fused steps put their results: one buffer of the plan, not one per call
 
     def autograd(scale=1.0):
         m.load_state_dict(sd)
@@ -254,6 +255,7 @@ def test_loss_and_backward_equals_autograd(classes, dtype):
         m.zero_grad(set_to_none=True)
         out = m.loss_and_backward(x, tgt, grad_scale=scale, dtype=dtype, loss=S)
         torch.cuda.synchronize()
+        ptrs.add(out.data_ptr())
         return out.clone(), m.flat_grads.detach().clone()
 
     l_a, g_a = autograd()
@@ -262,12 +264,14 @@ def test_loss_and_backward_equals_autograd(classes, dtype):
     assert abs(l_f[0].item() - l_a.item()) <= 1e-5 * abs(l_a.item())
     assert ((g_f - g_a).norm() / g_a.norm()).item() <= 1e-5
     assert torch.equal(S.last_components, l_f)
+    assert tuple(m.last_logits.shape) == (x.shape[0], classes) + tuple(x.shape[2:])
     assert l_f[2].item() > 0 and l_f[5].item() > 0 and l_f[1].item() == 0 and l_f[3].item() == 0 and l_f[4].item() == 0
     assert abs(l_f[0].item() - (0.5 * l_f[2].item() + l_f[5].item())) <= 1e-6 * abs(l_f[0].item())
     _, g_s = fused(scale=256.0)
     _, g_as = autograd(scale=256.0)
     assert torch.equal(g_s, g_as)
     assert ((g_s - 256.0 * g_f).norm() / (256.0 * g_f).norm()).item() <= 1e-5
+    assert len(ptrs) == 1
     # the default step is what it was: its own 4-float buffer, BCE + Dice or CE + Dice
     m.load_state_dict(sd)
     m.zero_grad(set_to_none=True)

@@ -19,76 +19,46 @@ reduction.
 A multi-class label outside [0, C) raises VkError (the kernel reports it through a device flag that is read back)."""
 from __future__ import annotations
 
+from functools import partial
+
 import torch
 import torch.nn as nn
 
 from . import _lib
 from ._lib import VkError, check, lib
+from ._lossfn import LossFn, check_target
 
 
-class _LossFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits, target, w_bce, w_dice):
-        if not logits.is_cuda:
-            raise VkError("loss input is on %s: no CPU fallback in this package" % logits.device)
-        x = logits.detach().contiguous().float()
-        y = target.detach().contiguous().float().expand_as(x).contiguous()
-        sums = torch.empty(8, dtype=torch.float64, device=x.device)
-        out = torch.empty(4, dtype=torch.float32, device=x.device)
-        need = logits.requires_grad
-        dl = torch.empty_like(x) if need else None
-        check(lib().vk_bce_dice_loss(x.numel(), x.data_ptr(), y.data_ptr(), sums.data_ptr(), out.data_ptr(),
-                                     _lib.ptr(dl), 1.0, float(w_bce), float(w_dice), _lib.current_stream()),
-              "vk_bce_dice_loss")
-        ctx.dl = dl
-        ctx.in_dtype = logits.dtype
-        return out[0].clone()
-
-    @staticmethod
-    def backward(ctx, g):
-        if ctx.dl is None:
-            return None, None, None, None
-        return (ctx.dl * g).to(ctx.in_dtype), None, None, None
+def _binary_run(w_bce, x, y, dl):
+    sums = torch.empty(8, dtype=torch.float64, device=x.device)
+    out = torch.empty(4, dtype=torch.float32, device=x.device)
+    check(lib().vk_bce_dice_loss(x.numel(), x.data_ptr(), y.data_ptr(), sums.data_ptr(), out.data_ptr(), _lib.ptr(dl), 1.0, w_bce, 1.0,
+                                 _lib.current_stream()), "vk_bce_dice_loss")
+    return out[0], None
 
 
-class _MultiLossFn(torch.autograd.Function):
-    """vk_multilabel_loss / vk_multiclass_loss on logits [N,C,H,W]: w_pix * (BCE or CE) + w_dice * Dice."""
+def _multi_run(multiclass, w_pix, x, y, dl):
+    """vk_multilabel_loss / vk_multiclass_loss on logits [N,C,H,W]: w_pix * (BCE or CE) + Dice."""
+    N, Cc, H, W = x.shape
+    L = lib()
+    ws = torch.empty(L.vk_multi_loss_workspace_bytes(N, Cc, H * W), dtype=torch.uint8, device=x.device)
+    out = torch.empty(4, dtype=torch.float32, device=x.device)
+    fn = L.vk_multiclass_loss if multiclass else L.vk_multilabel_loss
+    check(fn(N, Cc, H * W, x.data_ptr(), y.data_ptr(), ws.data_ptr(), ws.numel(), out.data_ptr(), _lib.ptr(dl), 1.0, w_pix, 1.0,
+             _lib.current_stream()), "vk_multiclass_loss" if multiclass else "vk_multilabel_loss")
+    return out[0], out[3] if multiclass else None          # out[3]: the device flag of out-of-range labels
 
-    @staticmethod
-    def forward(ctx, logits, target, multiclass, w_pix, w_dice):
-        if not logits.is_cuda:
-            raise VkError("loss input is on %s: no CPU fallback in this package" % logits.device)
-        if logits.dim() != 4:
-            raise ValueError("expected logits [N,C,H,W], got %s" % (tuple(logits.shape),))
-        N, Cc, H, W = logits.shape
-        x = logits.detach().contiguous().float()
-        if multiclass:
-            if tuple(target.shape) != (N, H, W) or target.dtype != torch.int64:
-                raise ValueError("DiceLoss('multiclass'): target must be int64 [N,H,W], got %s %s" % (target.dtype, tuple(target.shape)))
-            y = target.detach().contiguous()
-        else:
-            y = target.detach().float().expand_as(x).contiguous()
-        L = lib()
-        ws = torch.empty(L.vk_multi_loss_workspace_bytes(N, Cc, H * W), dtype=torch.uint8, device=x.device)
-        out = torch.empty(4, dtype=torch.float32, device=x.device)
-        dl = torch.empty_like(x) if logits.requires_grad else None
-        fn = L.vk_multiclass_loss if multiclass else L.vk_multilabel_loss
-        check(fn(N, Cc, H * W, x.data_ptr(), y.data_ptr(), ws.data_ptr(), ws.numel(), out.data_ptr(), _lib.ptr(dl), 1.0,
-                 float(w_pix), float(w_dice), _lib.current_stream()),
-              "vk_multiclass_loss" if multiclass else "vk_multilabel_loss")
-        if multiclass:
-            bad = int(out[3].item())          # the device flag of out-of-range labels (one host sync)
-            if bad:
-                raise VkError("multi-class target holds %d label(s) outside [0, %d)" % (bad, Cc))
-        ctx.dl = dl
-        ctx.in_dtype = logits.dtype
-        return out[0].clone()
 
-    @staticmethod
-    def backward(ctx, g):
-        if ctx.dl is None:
-            return None, None, None, None, None
-        return (ctx.dl * g).to(ctx.in_dtype), None, None, None, None
+def _apply(logits, target, mode, w_pix):
+    """``w_pix * (BCE or CE) + Dice`` of ``mode`` through the fused reduction of that mode."""
+    if not logits.is_cuda:
+        raise VkError("loss input is on %s: no CPU fallback in this package" % logits.device)
+    if mode == "binary":
+        return LossFn.apply(logits, target, partial(_binary_run, w_pix), False, None)
+    if logits.dim() != 4:
+        raise ValueError("expected logits [N,C,H,W], got %s" % (tuple(logits.shape),))
+    check_target(logits.shape, target, mode, "DiceLoss('multiclass')")
+    return LossFn.apply(logits, target, partial(_multi_run, mode == "multiclass", w_pix), mode == "multiclass", None)
 
 
 class DiceLoss(nn.Module):
@@ -105,9 +75,7 @@ class DiceLoss(nn.Module):
         self.mode = mode
 
     def forward(self, y_pred, y_true):
-        if self.mode == "binary":
-            return _LossFn.apply(y_pred, y_true, 0.0, 1.0)
-        return _MultiLossFn.apply(y_pred, y_true, self.mode == "multiclass", 0.0, 1.0)
+        return _apply(y_pred, y_true, self.mode, 0.0)
 
 
 class BCEDiceLoss(nn.Module):
@@ -122,13 +90,11 @@ class BCEDiceLoss(nn.Module):
         self.mode = mode
 
     def forward(self, y_pred, y_true):
-        if self.mode == "binary":
-            return _LossFn.apply(y_pred, y_true, 1.0, 1.0)
-        return _MultiLossFn.apply(y_pred, y_true, False, 1.0, 1.0)
+        return _apply(y_pred, y_true, self.mode, 1.0)
 
 
 class CEDiceLoss(nn.Module):
     """``CrossEntropyLoss()(x, t) + DiceLoss('multiclass')(x, t)`` in one reduction pass; t int64 [N,H,W] in [0, C)."""
 
     def forward(self, y_pred, y_true):
-        return _MultiLossFn.apply(y_pred, y_true, True, 1.0, 1.0)
+        return _apply(y_pred, y_true, "multiclass", 1.0)

@@ -31,7 +31,7 @@ from typing import Optional
 import torch
 import torch.nn as nn
 
-from . import _lib, seglosses
+from . import _lib, _lossfn, seglosses
 from ._lib import VkError, check, lib
 
 __all__ = ["LovaszLoss", "MCCLoss", "LossSum"]
@@ -47,14 +47,6 @@ class MCCLoss(seglosses._Term):
         if not (isinstance(eps, (int, float)) and math.isfinite(eps) and eps > 0):
             raise ValueError("MCCLoss: eps must be > 0, got %r" % (eps,))
         super().__init__("binary", None, dict(eps=float(eps)))
-
-
-def _weight(w):
-    if isinstance(w, bool) or not isinstance(w, (int, float)):
-        return None
-    if not math.isfinite(w):
-        raise ValueError("loss weight must be finite, got %r" % (w,))
-    return float(w)
 
 
 class _LovaszAlgebra:
@@ -75,7 +67,7 @@ class _LovaszAlgebra:
     __radd__ = __add__
 
     def __mul__(self, w):
-        w = _weight(w)
+        w = seglosses._weight(w)
         if w is None:
             return NotImplemented
         me = self._as_lovasz_sum()
@@ -110,46 +102,7 @@ class LovaszLoss(_LovaszAlgebra, nn.Module):
         return "mode=%r, per_image=%r, ignore_index=%r" % (self.mode, self.per_image, self.ignore_index)
 
 
-class _LovaszFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits, target, S):
-        N, Cc, H, W = logits.shape
-        HW = H * W
-        x = logits.detach().contiguous().float()
-        lcfg = S.lovasz_cfg(Cc)
-        multiclass = lcfg.mode == _lib.VK_LOSS_MULTICLASS
-        y = target.detach().contiguous() if multiclass else target.detach().float().expand_as(x).contiguous()
-        L = lib()
-        dl = torch.empty_like(x) if logits.requires_grad else None
-        st = _lib.current_stream()
-        out = torch.zeros(12, dtype=torch.float32, device=x.device)
-        if S.seg is not None:
-            scfg = S.seg.cfg(Cc)
-            sws = torch.empty(L.vk_seg_loss_workspace_bytes(N, Cc, HW), dtype=torch.uint8, device=x.device)
-            check(L.vk_seg_loss(scfg, N, Cc, HW, x.data_ptr(), y.data_ptr(), sws.data_ptr(), sws.numel(), out.data_ptr(), _lib.ptr(dl),
-                                1.0, st), "vk_seg_loss")
-        ws = S.workspace(lcfg, N, Cc, HW, x.device)
-        check(L.vk_lovasz_loss(lcfg, N, Cc, HW, x.data_ptr(), y.data_ptr(), ws.data_ptr(), ws.numel(), out[8:].data_ptr(), _lib.ptr(dl),
-                               S.w, 1 if S.seg is not None else 0, st), "vk_lovasz_loss")
-        if multiclass:
-            bad = int(out[9].item())          # labels that are neither a class nor ignore_index (one host sync, as vk.seglosses)
-            if bad:
-                raise VkError("multi-class target holds %d label(s) outside [0, %d)%s" % (
-                    bad, Cc, " other than ignore_index=%d" % lcfg.ignore_index if lcfg.has_ignore else ""))
-        total = out[0] + S.w * out[8]
-        S.last_components = torch.cat([total.reshape(1), out[1:6], out[7:9]])
-        ctx.dl = dl
-        ctx.in_dtype = logits.dtype
-        return total
-
-    @staticmethod
-    def backward(ctx, g):
-        if ctx.dl is None:
-            return None, None, None
-        return (ctx.dl * g).to(ctx.in_dtype), None, None
-
-
-class LossSum(_LovaszAlgebra, nn.Module):
+class LossSum(seglosses._Front, _LovaszAlgebra, nn.Module):
     """``seg`` (a ``vk.seglosses.LossSum`` or None) + ``w`` * ``term`` (a ``LovaszLoss``).  ``last_components``: device tensor
     [total, pix, focal, dice, jaccard, tversky, mcc, lovasz] of the last call (unweighted term values; no host sync)."""
 
@@ -157,7 +110,7 @@ class LossSum(_LovaszAlgebra, nn.Module):
         super().__init__()
         if not isinstance(term, LovaszLoss):
             raise TypeError("vk.lovasz.LossSum: the Lovasz term must be a LovaszLoss, got %s" % type(term).__name__)
-        w = _weight(w)
+        w = seglosses._weight(w)
         if w is None:
             raise TypeError("vk.lovasz.LossSum: the weight must be a number")
         ign = term.ignore_index
@@ -187,13 +140,7 @@ class LossSum(_LovaszAlgebra, nn.Module):
         return self
 
     def resolved_mode(self, C: int) -> str:
-        if self.mode == "binary" and C != 1:
-            raise ValueError("mode 'binary' needs logits with one channel, got %d" % C)
-        if self.mode == "multiclass" and C < 2:
-            raise ValueError("mode 'multiclass' needs C >= 2 channels, got %d" % C)
-        if not 1 <= C <= seglosses.MAX_CLASSES:
-            raise ValueError("expected 1 <= C <= %d classes, got %d" % (seglosses.MAX_CLASSES, C))
-        return self.mode
+        return _lossfn.check_classes(self.mode, C)
 
     def lovasz_cfg(self, C: int) -> "_lib.vk_lovasz_cfg":
         c = _lib.vk_lovasz_cfg()
@@ -220,32 +167,23 @@ class LossSum(_LovaszAlgebra, nn.Module):
             ws = self._ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
         return ws
 
-    def check_shapes(self, logits, target):
-        if logits.dim() != 4:
-            raise ValueError("expected logits [N,C,H,W], got %s" % (tuple(logits.shape),))
-        N, C, H, W = logits.shape
-        mode = self.resolved_mode(C)
-        if mode == "multiclass":
-            if tuple(target.shape) != (N, H, W) or target.dtype != torch.int64:
-                raise ValueError("mode 'multiclass': target must be int64 [N,H,W] = %s, got %s %s"
-                                 % ((N, H, W), target.dtype, tuple(target.shape)))
-        else:
-            try:
-                ok = tuple(torch.broadcast_shapes(tuple(target.shape), tuple(logits.shape))) == tuple(logits.shape)
-            except RuntimeError:
-                ok = False
-            if not ok:
-                raise ValueError("mode %r: target must broadcast to the logits' shape %s, got %s"
-                                 % (mode, tuple(logits.shape), tuple(target.shape)))
-        return mode
-
-    def forward(self, y_pred, y_true):
-        self.check_shapes(y_pred, y_true)
-        if not y_pred.is_cuda or not y_true.is_cuda:
-            raise VkError("loss input is on %s / %s: no CPU fallback in this package" % (y_pred.device, y_true.device))
-        if y_pred.dtype not in (torch.float32, torch.bfloat16, torch.float16):
-            raise ValueError("logits must be fp32, bf16 or fp16, got %s" % y_pred.dtype)
-        return _LovaszFn.apply(y_pred, y_true, self)
+    def _run(self, x, y, dl):
+        N, Cc, H, W = x.shape
+        HW = H * W
+        lcfg = self.lovasz_cfg(Cc)
+        L = lib()
+        st = _lib.current_stream()
+        out = torch.zeros(12, dtype=torch.float32, device=x.device)
+        if self.seg is not None:
+            sws = torch.empty(L.vk_seg_loss_workspace_bytes(N, Cc, HW), dtype=torch.uint8, device=x.device)
+            check(L.vk_seg_loss(self.seg.cfg(Cc), N, Cc, HW, x.data_ptr(), y.data_ptr(), sws.data_ptr(), sws.numel(), out.data_ptr(),
+                                _lib.ptr(dl), 1.0, st), "vk_seg_loss")
+        ws = self.workspace(lcfg, N, Cc, HW, x.device)
+        check(L.vk_lovasz_loss(lcfg, N, Cc, HW, x.data_ptr(), y.data_ptr(), ws.data_ptr(), ws.numel(), out[8:].data_ptr(), _lib.ptr(dl),
+                               self.w, 1 if self.seg is not None else 0, st), "vk_lovasz_loss")
+        total = out[0] + self.w * out[8]
+        self.last_components = torch.cat([total.reshape(1), out[1:6], out[7:9]])
+        return total, out[9] if lcfg.mode == _lib.VK_LOSS_MULTICLASS else None
 
     def extra_repr(self):
         return "w_lovasz=%r, mode=%r, ignore_index=%r" % (self.w, self.mode, self.ignore_index)

@@ -28,8 +28,9 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, _lossfn
 from ._lib import VkError, check, lib
+from ._lossfn import MAX_CLASSES
 from . import multiclass_eval as _mce
 
 __all__ = ["DiceLoss", "JaccardLoss", "TverskyLoss", "FocalLoss", "SoftBCEWithLogitsLoss", "SoftCrossEntropyLoss", "CrossEntropyLoss",
@@ -38,7 +39,6 @@ __all__ = ["DiceLoss", "JaccardLoss", "TverskyLoss", "FocalLoss", "SoftBCEWithLo
 MODES = ("binary", "multilabel", "multiclass")
 KINDS = ("pix", "focal", "dice", "jaccard", "tversky", "mcc")          # bit i of vk_seg_loss_cfg.terms; "mcc": vk.lovasz.MCCLoss
 _MODE_CODE = {"binary": _lib.VK_LOSS_BINARY, "multilabel": _lib.VK_LOSS_MULTILABEL, "multiclass": _lib.VK_LOSS_MULTICLASS}
-MAX_CLASSES = 16
 
 
 def _check_mode(mode, who):
@@ -52,6 +52,15 @@ def _check_ignore(ignore_index, who):
     if isinstance(ignore_index, bool) or int(ignore_index) != ignore_index or not -2 ** 31 <= int(ignore_index) < 2 ** 31:
         raise ValueError("%s: ignore_index must be an integer that fits 32 bits, got %r" % (who, ignore_index))
     return int(ignore_index)
+
+
+def _weight(w):
+    """a loss weight as a float; None for what is no number"""
+    if isinstance(w, bool) or not isinstance(w, (int, float)):
+        return None
+    if not math.isfinite(w):
+        raise ValueError("loss weight must be finite, got %r" % (w,))
+    return float(w)
 
 
 class _Algebra:
@@ -70,11 +79,10 @@ class _Algebra:
     __radd__ = __add__
 
     def __mul__(self, w):
-        if isinstance(w, bool) or not isinstance(w, (int, float)):
+        w = _weight(w)
+        if w is None:
             return NotImplemented
-        if not math.isfinite(w):
-            raise ValueError("loss weight must be finite, got %r" % (w,))
-        return LossSum([(float(w) * a, t) for a, t in self._as_sum().terms])
+        return LossSum([(w * a, t) for a, t in self._as_sum().terms])
 
     __rmul__ = __mul__
 
@@ -255,40 +263,26 @@ def MCCLoss(*a, **k):
     raise NotImplementedError("MCCLoss is not implemented here: use vk.lovasz.MCCLoss")
 
 
-class _SegLossFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits, target, loss_sum):
-        N, Cc, H, W = logits.shape
-        x = logits.detach().contiguous().float()
-        cfg = loss_sum.cfg(Cc)
-        if cfg.mode == _lib.VK_LOSS_MULTICLASS:
-            y = target.detach().contiguous()
-        else:
-            y = target.detach().float().expand_as(x).contiguous()
-        L = lib()
-        ws = torch.empty(L.vk_seg_loss_workspace_bytes(N, Cc, H * W), dtype=torch.uint8, device=x.device)
-        out = torch.empty(8, dtype=torch.float32, device=x.device)
-        dl = torch.empty_like(x) if logits.requires_grad else None
-        check(L.vk_seg_loss(cfg, N, Cc, H * W, x.data_ptr(), y.data_ptr(), ws.data_ptr(), ws.numel(), out.data_ptr(), _lib.ptr(dl), 1.0,
-                            _lib.current_stream()), "vk_seg_loss")
-        if cfg.mode == _lib.VK_LOSS_MULTICLASS:
-            bad = int(out[6].item())          # the device count of labels that are neither a class nor ignore_index (one host sync)
-            if bad:
-                raise VkError("multi-class target holds %d label(s) outside [0, %d)%s" % (
-                    bad, Cc, " other than ignore_index=%d" % cfg.ignore_index if cfg.has_ignore else ""))
-        loss_sum.last_components = out[:6]
-        ctx.dl = dl
-        ctx.in_dtype = logits.dtype
-        return out[0].clone()
+class _Front:
+    """What ``LossSum`` and ``vk.lovasz.LossSum`` share: the checks of a call and the autograd function around ``_run``."""
 
-    @staticmethod
-    def backward(ctx, g):
-        if ctx.dl is None:
-            return None, None, None
-        return (ctx.dl * g).to(ctx.in_dtype), None, None
+    def check_shapes(self, logits: torch.Tensor, target: torch.Tensor) -> str:
+        if logits.dim() != 4:
+            raise ValueError("expected logits [N,C,H,W], got %s" % (tuple(logits.shape),))
+        mode = self.resolved_mode(logits.shape[1])
+        _lossfn.check_target(logits.shape, target, mode)
+        return mode
+
+    def forward(self, y_pred, y_true):
+        mode = self.check_shapes(y_pred, y_true)
+        if not y_pred.is_cuda or not y_true.is_cuda:
+            raise VkError("loss input is on %s / %s: no CPU fallback in this package" % (y_pred.device, y_true.device))
+        if y_pred.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+            raise ValueError("logits must be fp32, bf16 or fp16, got %s" % y_pred.dtype)
+        return _lossfn.LossFn.apply(y_pred, y_true, self._run, mode == "multiclass", self.ignore_index)
 
 
-class LossSum(_Algebra, nn.Module):
+class LossSum(_Front, _Algebra, nn.Module):
     """A weighted sum of terms, computed by one ``vk_seg_loss`` call.  ``last_components``: device tensor
     [total, pix, focal, dice, jaccard, tversky] of the last call (unweighted term values, 0 for absent kinds; no host sync)."""
 
@@ -332,13 +326,7 @@ class LossSum(_Algebra, nn.Module):
 
     def resolved_mode(self, C: int) -> str:
         mode = self.mode if self.mode is not None else ("binary" if C == 1 else "multilabel")     # a BCE term alone: by C
-        if mode == "binary" and C != 1:
-            raise ValueError("mode 'binary' needs logits with one channel, got %d" % C)
-        if mode == "multiclass" and C < 2:
-            raise ValueError("mode 'multiclass' needs C >= 2 channels, got %d" % C)
-        if not 1 <= C <= MAX_CLASSES:
-            raise ValueError("expected 1 <= C <= %d classes, got %d" % (MAX_CLASSES, C))
-        return mode
+        return _lossfn.check_classes(mode, C)
 
     def spec(self, C: int) -> dict:
         """The sum as plain data: dict(mode, ignore_index, terms={kind: dict(w=weight, **options)}) with the options resolved for C
@@ -392,32 +380,16 @@ class LossSum(_Algebra, nn.Module):
         c.terms = terms
         return c
 
-    def check_shapes(self, logits: torch.Tensor, target: torch.Tensor) -> str:
-        if logits.dim() != 4:
-            raise ValueError("expected logits [N,C,H,W], got %s" % (tuple(logits.shape),))
-        N, C, H, W = logits.shape
-        mode = self.resolved_mode(C)
-        if mode == "multiclass":
-            if tuple(target.shape) != (N, H, W) or target.dtype != torch.int64:
-                raise ValueError("mode 'multiclass': target must be int64 [N,H,W] = %s, got %s %s"
-                                 % ((N, H, W), target.dtype, tuple(target.shape)))
-        else:
-            try:
-                ok = tuple(torch.broadcast_shapes(tuple(target.shape), tuple(logits.shape))) == tuple(logits.shape)
-            except RuntimeError:
-                ok = False
-            if not ok:
-                raise ValueError("mode %r: target must broadcast to the logits' shape %s, got %s"
-                                 % (mode, tuple(logits.shape), tuple(target.shape)))
-        return mode
-
-    def forward(self, y_pred, y_true):
-        self.check_shapes(y_pred, y_true)
-        if not y_pred.is_cuda or not y_true.is_cuda:
-            raise VkError("loss input is on %s / %s: no CPU fallback in this package" % (y_pred.device, y_true.device))
-        if y_pred.dtype not in (torch.float32, torch.bfloat16, torch.float16):
-            raise ValueError("logits must be fp32, bf16 or fp16, got %s" % y_pred.dtype)
-        return _SegLossFn.apply(y_pred, y_true, self)
+    def _run(self, x, y, dl):
+        N, Cc, H, W = x.shape
+        cfg = self.cfg(Cc)
+        L = lib()
+        ws = torch.empty(L.vk_seg_loss_workspace_bytes(N, Cc, H * W), dtype=torch.uint8, device=x.device)
+        out = torch.empty(8, dtype=torch.float32, device=x.device)
+        check(L.vk_seg_loss(cfg, N, Cc, H * W, x.data_ptr(), y.data_ptr(), ws.data_ptr(), ws.numel(), out.data_ptr(), _lib.ptr(dl), 1.0,
+                            _lib.current_stream()), "vk_seg_loss")
+        self.last_components = out[:6]
+        return out[0], out[6] if cfg.mode == _lib.VK_LOSS_MULTICLASS else None
 
     def extra_repr(self):
         return "weights=%r, mode=%r, ignore_index=%r" % ([w for w, _ in self.terms], self.mode, self.ignore_index)

@@ -21,7 +21,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, _lossfn
 from ._lib import VkError, check, lib
 
 
@@ -50,6 +50,7 @@ class _Plan:
         dev = model._flat["params"].device
         self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
         self.loss_out = torch.zeros(4, dtype=torch.float32, device=dev)
+        self._seg_out = self._lovasz_out = None       # the result buffers of the loss= routes: made at a route's first step on this plan
         self.weights_version = None
         self.mask = None                    # trainable flags the engine holds (vk_unet_set_trainable); None: not pushed yet
         self.bn_frozen = None               # BatchNorm modes the engine holds (vk_unet_set_bn_frozen); None: not pushed (all train)
@@ -97,6 +98,21 @@ class _Plan:
             self.dx = torch.empty(self.N, 3, self.H, self.W, dtype=torch.float32, device=device)
         check(lib().vk_unet_set_input_grad(self.h, self.dx.data_ptr() if on else None), "vk_unet_set_input_grad")
         self.dx_on = on
+
+    def seg_out(self) -> torch.Tensor:
+        """The 8 floats vk_unet_loss_cfg writes (loss=<vk.seglosses>)."""
+        if self._seg_out is None:
+            self._seg_out = torch.zeros(8, dtype=torch.float32, device=self.ws.device)
+        return self._seg_out
+
+    def lovasz_out(self):
+        """(the 16 floats vk_unet_loss_lovasz writes, the indices of the 8 that are reported, the 8 floats they are gathered into)."""
+        if self._lovasz_out is None:
+            dev = self.ws.device
+            self._lovasz_out = (torch.zeros(16, dtype=torch.float32, device=dev),
+                                torch.tensor([0, 1, 2, 3, 4, 5, 7, 8], dtype=torch.int64, device=dev),
+                                torch.empty(8, dtype=torch.float32, device=dev))
+        return self._lovasz_out
 
     def debug_tensor(self, name: str) -> torch.Tensor:
         """Copy of a named intermediate (NHWC) — parity/debug only."""
@@ -517,10 +533,30 @@ class Unet(nn.Module):
         if loss is not None:
             if mode is not None:
                 raise ValueError("loss_and_backward: give mode= or loss=, not both")
-            from . import lovasz
+            from . import lovasz, seglosses
             if isinstance(loss, lovasz._LovaszAlgebra):
-                return self._loss_lovasz_and_backward(x, y, grad_scale, dtype, loss._as_lovasz_sum())
-            return self._loss_cfg_and_backward(x, y, grad_scale, dtype, loss)
+                S = loss._as_lovasz_sum()
+                lcfg, scfg = S.lovasz_cfg(self.classes), S.seg_cfg(self.classes)
+
+                def launch(plan, logits, y, st):
+                    ws = S.workspace(lcfg, plan.N, self.classes, plan.H * plan.W, logits.device)
+                    check(lib().vk_unet_loss_lovasz(plan.h, scfg, lcfg, S.w, logits.data_ptr(), y.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                    plan.lovasz_out()[0].data_ptr(), float(grad_scale), st), "vk_unet_loss_lovasz")
+
+                plan = self._fused_step(x, y, dtype, lcfg.mode == _lib.VK_LOSS_MULTICLASS, "loss=<multiclass>", True, launch)
+                out, pick, picked = plan.lovasz_out()
+                S.last_components = torch.index_select(out, 0, pick, out=picked)
+                return picked
+            S = seglosses.as_loss_sum(loss)
+            cfg = S.cfg(self.classes)
+
+            def launch(plan, logits, y, st):
+                check(lib().vk_unet_loss_cfg(plan.h, cfg, logits.data_ptr(), y.data_ptr(), plan.seg_out().data_ptr(), float(grad_scale),
+                                             st), "vk_unet_loss_cfg")
+
+            plan = self._fused_step(x, y, dtype, cfg.mode == _lib.VK_LOSS_MULTICLASS, "loss=<multiclass>", True, launch)
+            S.last_components = plan.seg_out()[:6]
+            return S.last_components
         if mode is None:
             if self.classes != 1:
                 raise ValueError("loss_and_backward: classes=%d needs mode='multilabel' or mode='multiclass'" % self.classes)
@@ -528,89 +564,37 @@ class Unet(nn.Module):
         codes = {"binary": _lib.VK_LOSS_BINARY, "multilabel": _lib.VK_LOSS_MULTILABEL, "multiclass": _lib.VK_LOSS_MULTICLASS}
         if mode not in codes:
             raise ValueError("loss_and_backward: unknown mode %r" % (mode,))
+
+        def launch(plan, logits, y, st):
+            if mode == "binary":
+                check(lib().vk_unet_loss(plan.h, logits.data_ptr(), y.data_ptr(), plan.loss_out.data_ptr(), float(grad_scale),
+                                         1.0, 1.0, st), "vk_unet_loss")
+            else:
+                check(lib().vk_unet_loss_ex(plan.h, codes[mode], logits.data_ptr(), y.data_ptr(), plan.loss_out.data_ptr(),
+                                            float(grad_scale), 1.0, 1.0, st), "vk_unet_loss_ex")
+
+        return self._fused_step(x, y, dtype, mode == "multiclass", "mode='multiclass'", False, launch).loss_out[:3]
+
+    def _fused_step(self, x, y, dtype, multiclass: bool, who: str, nchw: bool, launch) -> _Plan:
+        """The step every route of ``loss_and_backward`` runs; returns the plan, whose buffer ``launch(plan, logits, y, stream)`` made
+        the engine's loss kernel write.  ``who`` names the route in the message about a multiclass target; ``nchw``: the ``loss=``
+        routes, which also refuse a sigmoid-mode target that is not [N, 1 or classes, H, W]."""
         self._check_input(x)
         mask = self._trainable_mask()
         if not any(mask):
             raise VkError("loss_and_backward: no parameter requires grad (every tensor is frozen)")
         N, _, H, W = x.shape
-        plan = self.plan_for(N, H if H == W else (H, W), dtype or self.compute_dtype, True)
-        if mode == "multiclass" and (tuple(y.shape) != (N, H, W) or y.dtype != torch.int64):
-            raise ValueError("loss_and_backward(mode='multiclass'): target must be int64 [N,H,W], got %s %s" % (y.dtype, tuple(y.shape)))
-        logits = self._run_forward(plan, x, True)
-        if mode == "multiclass":
-            y = y.detach().contiguous()
-        elif mode == "multilabel":
-            y = y.detach().float().expand(N, self.classes, H, W).contiguous()
-        else:
-            y = y.detach().contiguous().float()
-        if mode == "binary":
-            check(lib().vk_unet_loss(plan.h, logits.data_ptr(), y.data_ptr(), plan.loss_out.data_ptr(), float(grad_scale),
-                                     1.0, 1.0, _lib.current_stream()), "vk_unet_loss")
-        else:
-            check(lib().vk_unet_loss_ex(plan.h, codes[mode], logits.data_ptr(), y.data_ptr(), plan.loss_out.data_ptr(),
-                                        float(grad_scale), 1.0, 1.0, _lib.current_stream()), "vk_unet_loss_ex")
-        self._run_backward(plan, None, mask)
-        self.last_logits = logits
-        return plan.loss_out[:3]
-
-
-    def _loss_cfg_and_backward(self, x, y, grad_scale, dtype, loss) -> torch.Tensor:
-        from . import seglosses
-        S = seglosses.as_loss_sum(loss)
-        self._check_input(x)
-        mask = self._trainable_mask()
-        if not any(mask):
-            raise VkError("loss_and_backward: no parameter requires grad (every tensor is frozen)")
-        N, _, H, W = x.shape
-        cfg = S.cfg(self.classes)
-        multiclass = cfg.mode == _lib.VK_LOSS_MULTICLASS
+        shape = (N, self.classes, H, W)
         if multiclass:
-            if tuple(y.shape) != (N, H, W) or y.dtype != torch.int64:
-                raise ValueError("loss_and_backward(loss=<multiclass>): target must be int64 [N,H,W], got %s %s" % (y.dtype, tuple(y.shape)))
-        elif y.dim() != 4 or y.shape[0] != N or y.shape[1] not in (1, self.classes) or tuple(y.shape[2:]) != (H, W):
+            _lossfn.check_target(shape, y, "multiclass", "loss_and_backward(%s)" % who)
+        elif nchw and (y.dim() != 4 or y.shape[0] != N or y.shape[1] not in (1, self.classes) or tuple(y.shape[2:]) != (H, W)):
             raise ValueError("loss_and_backward(loss=...): target must be [N,%d,H,W], got %s" % (self.classes, tuple(y.shape)))
         plan = self.plan_for(N, H if H == W else (H, W), dtype or self.compute_dtype, True)
-        logits = self._run_forward(plan, x, True)
-        y = y.detach().contiguous() if multiclass else y.detach().float().expand(N, self.classes, H, W).contiguous()
-        out = getattr(plan, "seg_loss_out", None)
-        if out is None:
-            out = plan.seg_loss_out = torch.zeros(8, dtype=torch.float32, device=logits.device)
-        check(lib().vk_unet_loss_cfg(plan.h, cfg, logits.data_ptr(), y.data_ptr(), out.data_ptr(), float(grad_scale),
-                                     _lib.current_stream()), "vk_unet_loss_cfg")
+        logits, y = _lossfn.marshal(self._run_forward(plan, x, True), y, multiclass)
+        launch(plan, logits, y, _lib.current_stream())
         self._run_backward(plan, None, mask)
         self.last_logits = logits
-        S.last_components = out[:6]
-        return out[:6]
-
-
-    def _loss_lovasz_and_backward(self, x, y, grad_scale, dtype, S) -> torch.Tensor:
-        lcfg = S.lovasz_cfg(self.classes)
-        scfg = S.seg_cfg(self.classes)
-        self._check_input(x)
-        mask = self._trainable_mask()
-        if not any(mask):
-            raise VkError("loss_and_backward: no parameter requires grad (every tensor is frozen)")
-        N, _, H, W = x.shape
-        multiclass = lcfg.mode == _lib.VK_LOSS_MULTICLASS
-        if multiclass:
-            if tuple(y.shape) != (N, H, W) or y.dtype != torch.int64:
-                raise ValueError("loss_and_backward(loss=<multiclass>): target must be int64 [N,H,W], got %s %s" % (y.dtype, tuple(y.shape)))
-        elif y.dim() != 4 or y.shape[0] != N or y.shape[1] not in (1, self.classes) or tuple(y.shape[2:]) != (H, W):
-            raise ValueError("loss_and_backward(loss=...): target must be [N,%d,H,W], got %s" % (self.classes, tuple(y.shape)))
-        plan = self.plan_for(N, H if H == W else (H, W), dtype or self.compute_dtype, True)
-        logits = self._run_forward(plan, x, True)
-        y = y.detach().contiguous() if multiclass else y.detach().float().expand(N, self.classes, H, W).contiguous()
-        out = getattr(plan, "lovasz_loss_out", None)
-        if out is None:
-            out = plan.lovasz_loss_out = torch.zeros(16, dtype=torch.float32, device=logits.device)
-            plan.lovasz_pick = torch.tensor([0, 1, 2, 3, 4, 5, 7, 8], dtype=torch.int64, device=logits.device)
-        ws = S.workspace(lcfg, N, self.classes, H * W, logits.device)
-        check(lib().vk_unet_loss_lovasz(plan.h, scfg, lcfg, S.w, logits.data_ptr(), y.data_ptr(), ws.data_ptr(), ws.numel(),
-                                        out.data_ptr(), float(grad_scale), _lib.current_stream()), "vk_unet_loss_lovasz")
-        self._run_backward(plan, None, mask)
-        self.last_logits = logits
-        S.last_components = out.index_select(0, plan.lovasz_pick)
-        return S.last_components
+        return plan
 
 
 def build_model(encoder: str = "resnet34", weights: Optional[str] = "imagenet") -> Unet:

@@ -56,6 +56,8 @@ class _Plan:
         self.bn_frozen = None               # BatchNorm modes the engine holds (vk_unet_set_bn_frozen); None: not pushed (all train)
         self.dx: Optional[torch.Tensor] = None     # fp32 [N,3,H,W] input gradient the engine writes (vk_unet_set_input_grad)
         self.dx_on = False
+        self.serial = 0                     # forwards this plan has run; a graph remembers the value its own forward left (_UnetFn)
+        self.last_forward = ""              # what ran that forward, for the message of a displaced graph
         self.bucket_trainable: List[bool] = []
         self.nbuckets = L.vk_unet_num_buckets(h)
         self.buckets: List[Tuple[int, int]] = []
@@ -143,11 +145,21 @@ class _UnetFn(torch.autograd.Function):
     def forward(ctx, x, anchor, model, plan, mask):
         ctx.model, ctx.plan, ctx.mask = model, plan, mask      # requires_grad as it was when the forward ran (torch records it then)
         ctx.x_dtype, ctx.x_device = x.dtype, x.device
-        return model._run_forward(plan, x, True)
+        logits = model._run_forward(plan, x, True, "a forward with a graph (model(x) in grad mode)")
+        ctx.serial = plan.serial           # the plan's workspace holds THIS forward's activations while the two are equal
+        return logits
 
     @staticmethod
     def backward(ctx, g):
         want_dx = bool(ctx.needs_input_grad[0])
+        plan = ctx.plan
+        if plan.serial != ctx.serial:      # before anything is written: the gradients and every .grad stay as they are
+            raise VkError("backward() through a forward whose activations are gone: the plan (N=%d, %dx%d, %s) has since run %s, "
+                          "which overwrote them (%d forward(s) later). One plan holds the activations of one forward: call backward() "
+                          "before the next forward of that shape and dtype (model(x), a torch.no_grad() forward or loss_and_backward), "
+                          "see INTEGRATION.md \"One forward per shape at a time\""
+                          % (plan.N, plan.H, plan.W, str(plan.dtype).replace("torch.", ""), plan.last_forward,
+                             plan.serial - ctx.serial))
         ctx.model._run_backward(ctx.plan, g.contiguous().float(), ctx.mask, want_dx)
         # the plan's buffer is rewritten by the next backward: hand autograd a copy in x's dtype
         dx = ctx.plan.dx.to(dtype=ctx.x_dtype, copy=True) if want_dx else None
@@ -410,8 +422,10 @@ class Unet(nn.Module):
         if self._flat["params"].device != x.device:
             raise VkError("model is on %s but the input is on %s" % (self._flat["params"].device, x.device))
 
-    def _run_forward(self, plan: _Plan, x: torch.Tensor, training: bool) -> torch.Tensor:
+    def _run_forward(self, plan: _Plan, x: torch.Tensor, training: bool, who: str = "a forward without a graph") -> torch.Tensor:
         L = lib()
+        plan.serial += 1                    # whatever graph an earlier forward of this plan left can no longer run its backward
+        plan.last_forward = who
         st = _lib.current_stream()
         ver = self._weights_version()
         if plan.weights_version != ver:
@@ -513,7 +527,7 @@ class Unet(nn.Module):
         plan = self.plan_for(N, S, dtype, need_grad or not all_frozen)
         if need_grad:
             return _UnetFn.apply(x, self._anchor, self, plan, mask)
-        return self._run_forward(plan, x, not all_frozen)
+        return self._run_forward(plan, x, not all_frozen, "a forward without a graph (torch.no_grad(), or nothing requires grad)")
 
     # ------------------------------------------------------------------ fused step (no autograd graph)
     def loss_and_backward(self, x: torch.Tensor, y: torch.Tensor, grad_scale: float = 1.0,
@@ -590,7 +604,7 @@ class Unet(nn.Module):
         elif nchw and (y.dim() != 4 or y.shape[0] != N or y.shape[1] not in (1, self.classes) or tuple(y.shape[2:]) != (H, W)):
             raise ValueError("loss_and_backward(loss=...): target must be [N,%d,H,W], got %s" % (self.classes, tuple(y.shape)))
         plan = self.plan_for(N, H if H == W else (H, W), dtype or self.compute_dtype, True)
-        logits, y = _lossfn.marshal(self._run_forward(plan, x, True), y, multiclass)
+        logits, y = _lossfn.marshal(self._run_forward(plan, x, True, "loss_and_backward"), y, multiclass)
         launch(plan, logits, y, _lib.current_stream())
         self._run_backward(plan, None, mask)
         self.last_logits = logits

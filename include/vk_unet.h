@@ -831,6 +831,92 @@ int vk_inst_match(int batch, int Mp, int Mg, const int32_t* table, const int32_t
                   size_t diag_gt_stride, int32_t* pair_gt, double* pair_iou, double* pair_derr, vk_inst_stats* per_image,
                   vk_inst_stats* totals, int accumulate, void* stream);
 
+/* Sub-pixel vertex refinement of the indentation fit (subpix.hip).  vk_geom_det and vk_geom_quad carry int32 corners, so their
+ * diagonals are quantised to a map pixel at either tip.  This call moves each of the four corners of every record to where the
+ * probability map the fit was made from puts it, in float64, and forms the diagonals again.  One launch, one 256-thread workgroup per
+ * (image, slot), wave k refines vertex k; no workspace, no atomics, no synchronisation.
+ *
+ * prob: device float32 [batch][h][w], the map the geometry call read (h, w >= 1, h * w < 2^30, batch 1..65535).  records: the
+ * geometry call's `dets`, read in place: slot s of image b is at (char*)records + ((size_t)b * max_components + s) * record_stride; it
+ * begins with int label, int area, holds int box[8] at box_offset and, when valid_offset >= 0, int valid there (the quadrilateral fit;
+ * -1 for the rectangle fit: every record is valid).  record_stride and the offsets are multiples of 4.  counts: device int32 [batch],
+ * max_components 1..4096.  affine (optional): device double [batch][3] = (ox, oy, inv_scale), the letterbox geometry of each image;
+ * NULL means (0, 0, 1).  out: device vk_subpix_quad [batch][max_components], 8-byte aligned.
+ *
+ * Only the slots 0 .. min(counts[b], max_components) - 1 are written (a negative count as 0), every byte of them; nothing else is
+ * touched.  A record with valid == 0 gives label, area, valid = 0 and zeros in every other field.  Otherwise v holds the refined
+ * vertices in map coordinates in the record's order, vs[2 i] = (v[2 i] - ox) * inv_scale, vs[2 i + 1] = (v[2 i + 1] - oy) * inv_scale,
+ * and the diagonals follow the rule of the geometry records on v in float64: d = sqrt(dx * dx + dy * dy) of the six pairs in the order
+ * (0,1) (0,2) (0,3) (1,2) (1,3) (2,3), the first longest one is the first diagonal, the other two vertices give the second;
+ * d1 = dmax * inv_scale, d2 = sqrt(ex * ex + ey * ey) * inv_scale, d_mean = 0.5 * (d1 + d2).
+ *
+ * Arithmetic: IEEE float64, contraction off, only + - * / sqrt floor fabs and compares on the device; every expression below is
+ * evaluated as written, left to right inside its parentheses.
+ *   sample(x, y):  x = x > 0 ? x : 0;  x = x < w - 1 ? x : w - 1 (so a NaN becomes 0); y likewise with h;
+ *     x0 = min((int)floor(x), w - 2), or 0 when w == 1; x1 = x0 + 1, or 0 when w == 1; y0, y1 likewise; fx = x - x0, fy = y - y0;
+ *     top = p[y0][x0] * (1 - fx) + p[y0][x1] * fx;  bot = p[y1][x0] * (1 - fx) + p[y1][x1] * fx;  value = top * (1 - fy) + bot * fy.
+ *
+ * method VK_SUBPIX_CORNER, gradient orthogonality (the iteration OpenCV documents for cornerSubPix).  win 2..15, zero_zone -1..win - 1,
+ * max_iter 1..100, eps > 0, wt[2 win + 1] finite (the caller's exp(-((k - win) / win)^2): no transcendental runs on the device).
+ * q = the int32 vertex.  Per iteration: S[j][i] = sample(q.x + (i - win - 1), q.y + (j - win - 1)), i, j = 0 .. 2 win + 2.  For
+ * j, i = 0 .. 2 win: px = i - win, py = j - win, m = wt[j] * wt[i], or 0 when zero_zone >= 0 and |px| <= zero_zone and
+ * |py| <= zero_zone; gx = S[j+1][i+2] - S[j+1][i], gy = S[j+2][i+1] - S[j][i+1]; gxx = gx * gx, gxy = gx * gy, gyy = gy * gy;
+ * the row sums, i ascending from 0.0: ra += m * gxx, rb += m * gxy, rc += m * gyy, r1 += m * (gxx * px + gxy * py),
+ * r2 += m * (gxy * px + gyy * py); then a, b, c, bb1, bb2 from 0.0 over the row sums, j ascending.  det = a * c - b * b.  Unless
+ * fabs(det) > DBL_EPSILON * DBL_EPSILON and det is finite: flag SINGULAR, stop.  step = ((c * bb1 - b * bb2) / det,
+ * (a * bb2 - b * bb1) / det); q += step; iters += 1.  Then, in this order: step.x * step.x + step.y * step.y <= eps * eps: stop
+ * (converged); unless 0 <= q.x < w and 0 <= q.y < h: flag LEFT_MAP, stop; iters == max_iter: flag NOT_CONVERGED, stop.  Afterwards,
+ * unless fabs(q.x - start.x) <= win and fabs(q.y - start.y) <= win (a NaN fails): q = start, flag RESTORED.
+ *
+ * method VK_SUBPIX_LINES, the two sides that meet at the vertex.  0 <= lo < hi <= 1, n_stations 3..32, reach R 1..15, level finite,
+ * max_shift > 0.  centre = (((x0 + x1) + x2) + x3) * 0.25 of the start vertices, y likewise.  For vertex i, the sides towards
+ * j = (i + 1) & 3 and then j = (i + 3) & 3: d = V_j - V_i, L = sqrt(d.x * d.x + d.y * d.y); L < 8: flag SHORT_SIDE.
+ * n = (d.y / L, -d.x / L), negated when n.x * (V_i.x - centre.x) + n.y * (V_i.y - centre.y) < 0.  Station k = 0 .. n_stations - 1:
+ * f = lo + ((hi - lo) * k) / (n_stations - 1), s = (V_i.x + d.x * f, V_i.y + d.y * f), g_t = sample(s.x + t * n.x, s.y + t * n.y) for
+ * t = -R .. R.  For t = -R .. R - 1 ascending, where g_t >= level and level > g_t+1: pos = t + (g_t - level) / (g_t - g_t+1), taken
+ * when fabs(pos) is below the best so far (which starts at +inf, so a NaN never wins and the smaller t wins a tie); the station's
+ * point is (s.x + pos * n.x, s.y + pos * n.y).  Fewer than three points on a side: flag NO_EDGE.  Otherwise total least squares over
+ * the points in station order: sums of x and y from 0.0, centroid c = sum / count; sxx, syy, sxy from 0.0 over dx * dx, dy * dy,
+ * dx * dy with dx = x - c.x, dy = y - c.y; hs = (sxx + syy) * 0.5, hd = (sxx - syy) * 0.5, lam = hs + sqrt(hd * hd + sxy * sxy);
+ * direction v = (sxy, lam - sxx) when fabs(lam - sxx) > fabs(lam - syy), else (lam - syy, sxy).  With a flag from either side the
+ * vertex keeps its start.  Otherwise den = v1.x * v2.y - v1.y * v2.x; unless den * den > 1e-6 * ((v1.x * v1.x + v1.y * v1.y) *
+ * (v2.x * v2.x + v2.y * v2.y)): flag PARALLEL, start kept.  e = c2 - c1, u = (e.x * v2.y - e.y * v2.x) / den,
+ * q = (c1.x + u * v1.x, c1.y + u * v1.y); unless fabs(q.x - start.x) <= max_shift and fabs(q.y - start.y) <= max_shift: start kept, flag
+ * RESTORED.  iters[i] counts the points found on the two sides. */
+#define VK_SUBPIX_CORNER 0
+#define VK_SUBPIX_LINES 1
+#define VK_SUBPIX_MAX_WIN 15
+#define VK_SUBPIX_MAX_REACH 15
+#define VK_SUBPIX_MAX_STATIONS 32
+#define VK_SUBPIX_SINGULAR 1
+#define VK_SUBPIX_LEFT_MAP 2
+#define VK_SUBPIX_NOT_CONVERGED 4
+#define VK_SUBPIX_RESTORED 8
+#define VK_SUBPIX_SHORT_SIDE 16
+#define VK_SUBPIX_NO_EDGE 32
+#define VK_SUBPIX_PARALLEL 64
+typedef struct vk_subpix_params {
+  int method;                   /* VK_SUBPIX_CORNER / VK_SUBPIX_LINES; the other method's fields are not read */
+  int win, zero_zone, max_iter; /* corner */
+  double eps;
+  double wt[2 * VK_SUBPIX_MAX_WIN + 1];
+  int n_stations, reach;        /* lines */
+  double lo, hi, level, max_shift;
+} vk_subpix_params;
+typedef struct vk_subpix_quad {
+  int label, area;              /* copied from the source record */
+  int valid;                    /* 1, or 0 for a quadrilateral record with valid == 0 */
+  int reserved;                 /* written as 0 */
+  int flags[4];                 /* per vertex, VK_SUBPIX_* bits; 0: refined without remark */
+  int iters[4];
+  double v[8];                  /* x0,y0 .. x3,y3 in map coordinates */
+  double vs[8];                 /* the same in source-image coordinates */
+  double d1, d2, d_mean;        /* in source-image pixels */
+} vk_subpix_quad;
+int vk_subpix_refine(const vk_subpix_params* params, int batch, int h, int w, const float* prob, const void* records,
+                     size_t record_stride, size_t box_offset, int valid_offset, const int32_t* counts, int max_components,
+                     const double* affine, vk_subpix_quad* out, void* stream);
+
 /* AdamW (decoupled decay) over a flat fp32 parameter buffer; optionally emits the 16-bit working copy.
  * inv_scale multiplies the gradient first (GradScaler unscale / data-parallel averaging).
  * found_inf (optional int*): when *found_inf != 0 on the device the step is skipped: param, the moments and lowp_copy stay unwritten.

@@ -121,6 +121,23 @@ class vk_inst_stats(C.Structure):
     _fields_ = [(f, C.c_int64) for f in INST_INT_FIELDS] + [(f, C.c_double) for f in INST_FLOAT_FIELDS]
 
 
+VK_SUBPIX_CORNER, VK_SUBPIX_LINES = 0, 1
+VK_SUBPIX_MAX_WIN, VK_SUBPIX_MAX_REACH, VK_SUBPIX_MAX_STATIONS = 15, 15, 32
+SUBPIX_FLAGS = {"singular": 1, "left_map": 2, "not_converged": 4, "restored": 8, "short_side": 16, "no_edge": 32, "parallel": 64}
+
+
+class vk_subpix_params(C.Structure):
+    _fields_ = [("method", C.c_int), ("win", C.c_int), ("zero_zone", C.c_int), ("max_iter", C.c_int), ("eps", C.c_double),
+                ("wt", C.c_double * (2 * VK_SUBPIX_MAX_WIN + 1)), ("n_stations", C.c_int), ("reach", C.c_int), ("lo", C.c_double),
+                ("hi", C.c_double), ("level", C.c_double), ("max_shift", C.c_double)]
+
+
+class vk_subpix_quad(C.Structure):
+    _fields_ = [("label", C.c_int), ("area", C.c_int), ("valid", C.c_int), ("reserved", C.c_int), ("flags", C.c_int * 4),
+                ("iters", C.c_int * 4), ("v", C.c_double * 8), ("vs", C.c_double * 8), ("d1", C.c_double), ("d2", C.c_double),
+                ("d_mean", C.c_double)]
+
+
 class vk_adamw_group(C.Structure):
     _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float)]
 
@@ -224,6 +241,7 @@ SIGNATURES = {
     "vk_sweep_curves": (ci, [ci, ci, ci, vp, vp, ci, cf, vp, sz, vp, sz, vp]),
     "vk_inst_contingency": (ci, [ci, ci, ci, vp, vp, ci, ci, vp, vp]),
     "vk_inst_match": (ci, [ci, ci, ci, vp, vp, vp, ci, vp, vp, sz, vp, sz, vp, vp, vp, vp, vp, ci, vp]),
+    "vk_subpix_refine": (ci, [P(vk_subpix_params), ci, ci, ci, vp, vp, sz, sz, ci, vp, ci, vp, vp, vp]),
     "vk_adamw_step": (ci, [sz, vp, vp, vp, vp, cf, cf, cf, cf, cf, ci, cf, vp, vp, ci, vp]),
     "vk_amp_check_inf": (ci, [sz, vp, vp, vp]),
     "vk_amp_unscale_check": (ci, [sz, vp, vp, vp, vp]),

@@ -255,14 +255,20 @@ def summarize(totals: np.ndarray, thresholds=None) -> Dict[str, np.ndarray]:
 class ObjectMetrics:
     """The object metrics over an epoch: ``update(prob, target)`` per validation batch of any size, ``compute()`` at the end.
     ``update`` synchronises with nothing; ``compute`` reads the totals back once.  ``pred_args`` go to ``detect`` for the prediction;
-    the target is detected with the ground-truth preset."""
+    the target is detected with the ground-truth preset.  ``refine``: None, or a dict of ``vk.subpix.refine`` arguments (``method``,
+    ``affine``, its parameters): then the corners of both the prediction's and the target's records are refined below a pixel before
+    the diagonals are compared."""
 
-    def __init__(self, fit: str = "rect", iou_thresholds=None, max_components: int = 64, fit_outset_px: int = G.FIT_OUTSET_PX, **pred_args):
+    def __init__(self, fit: str = "rect", iou_thresholds=None, max_components: int = 64, fit_outset_px: int = G.FIT_OUTSET_PX,
+                 refine: Optional[dict] = None, **pred_args):
         if fit not in _FITS:
             raise ValueError("fit must be 'rect' or 'quad', got %r" % (fit,))
         if not 1 <= int(max_components) <= MAX_SLOTS:
             raise ValueError("max_components %r outside 1..%d" % (max_components, MAX_SLOTS))
+        if refine is not None and not isinstance(refine, dict):
+            raise ValueError("refine must be None or a dict of vk.subpix.refine arguments, got %r" % (refine,))
         self.thresholds = _iou_thresholds(iou_thresholds)
+        self.refine = None if refine is None else dict(refine)
         self.fit, self.max_components, self.fit_outset_px, self.pred_args = fit, int(max_components), int(fit_outset_px), dict(pred_args)
         self.reset()
 
@@ -280,6 +286,9 @@ class ObjectMetrics:
             raise VkError("object metrics take CUDA tensors (%s / %s): no CPU fallback in this package" % (prob.device, target.device))
         pred = detect(prob, fit=self.fit, fit_outset_px=self.fit_outset_px, max_components=self.max_components, **self.pred_args)
         gt = detect_gt(target, fit=self.fit, fit_outset_px=self.fit_outset_px, max_components=self.max_components)
+        if self.refine is not None:
+            from . import subpix
+            pred, gt = subpix.refine(pred, prob, **self.refine), subpix.refine(gt, target.float(), **self.refine)
         res = match(pred, gt, self.thresholds, totals=self._totals)
         self._totals = res.totals
         self._images += int(prob.shape[0])
@@ -295,8 +304,8 @@ class ObjectMetrics:
 
 
 def object_metrics(prob: torch.Tensor, target: torch.Tensor, fit: str = "rect", iou_thresholds=None, max_components: int = 64,
-                   fit_outset_px: int = G.FIT_OUTSET_PX, **pred_args) -> Dict[str, np.ndarray]:
+                   fit_outset_px: int = G.FIT_OUTSET_PX, refine: Optional[dict] = None, **pred_args) -> Dict[str, np.ndarray]:
     """Everything in one call: detect both, count, match, summarise.  One read-back at the end."""
-    om = ObjectMetrics(fit, iou_thresholds, max_components, fit_outset_px, **pred_args)
+    om = ObjectMetrics(fit, iou_thresholds, max_components, fit_outset_px, refine=refine, **pred_args)
     om.update(prob, target)
     return om.compute()

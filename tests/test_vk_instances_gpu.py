@@ -295,3 +295,71 @@ def test_end_to_end_real_masks(vk, idx, shift):
     cfg = GC.Cfg(thresh=0.5, k=1, min_area=4, cap=64, outset=1)
     d, tot = _e2e(vk, prob[None], tgt[None], "rect", cfg)
     assert tot["n_gt_used"][0] >= 1
+
+
+# ================================================================================================ one front end
+def _lists_equal(got, want, tag):
+    assert len(got) == len(want), (tag, len(got), len(want))
+    for i, (a, b) in enumerate(zip(got, want)):
+        assert list(a) == list(b), (tag, i, list(a), list(b))
+        for k in a:
+            if isinstance(b[k], np.ndarray):
+                assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape and a[k].tobytes() == b[k].tobytes(), (tag, i, k, a[k], b[k])
+            else:
+                assert type(a[k]) is type(b[k]) and a[k] == b[k], (tag, i, k, a[k], b[k])
+
+
+def _both_paths(vk, fit, tp, cap, outset, **kw):
+    """detect with and without the slot map and the reference-shaped batch function on the same maps, the 200-pixel floor deciding."""
+    Gm = vk.geometry
+    full = vk.instances.detect(tp, fit=fit, min_area=200, fit_outset_px=outset, max_components=cap, **kw)
+    bare = vk.instances.detect(tp, fit=fit, min_area=200, fit_outset_px=outset, max_components=cap, slots=False, **kw)
+    assert bare.slots is None and full.slots is not None and full.slots.dtype == torch.int32 and full.slots.shape == tp.shape
+    for name in ("clean", "raw", "counts"):
+        a, b = getattr(full, name), getattr(bare, name)
+        assert a.dtype == b.dtype and a.shape == b.shape and torch.equal(a, b), (fit, name)
+    if fit == "rect":
+        clean, lists = vk.postprocess_minarearect_batch(tp, min_area_frac=0.0, max_components=cap, **kw)
+    else:
+        clean, lists = vk.postprocess_quadrilateral_batch(tp, min_area_frac=0.0, fit_outset_px=outset, max_components=cap, **kw)
+    assert clean.dtype == torch.uint8 and torch.equal(clean, bare.clean)
+    rows = bare.records()
+    to_dicts = Gm._records if fit == "rect" else Gm._quad_records
+    assert len(lists) == len(rows) == tp.shape[0]
+    for b in range(len(rows)):
+        _lists_equal(lists[b], to_dicts(rows[b]), (fit, b))
+    return bare, rows, lists
+
+
+@pytest.mark.parametrize("fit", ["rect", "quad"])
+def test_front_end_paths_agree(vk, fit):
+    prob, _ = IC.squares_case()
+    cfg = IC.E2E_CFG
+    bare, rows, lists = _both_paths(vk, fit, torch.from_numpy(prob).to(_dev()), cfg.cap, cfg.outset, bin_thresh=cfg.thresh,
+                                    morph_kernel=cfg.k, open_iter=cfg.oi, close_iter=cfg.ci)
+    # instances_ref.detect_ref at min_area 200: areas 545, 321, 621 / 816, 373, 373 (the extra square of image 0 is below the floor)
+    assert bare.counts.cpu().tolist() == [3, 3] and [r["area"].tolist() for r in rows] == [[545, 321, 621], [816, 373, 373]]
+    assert [[d["area"] for d in lst] for lst in lists] == [[621, 545, 321], [816, 373, 373]]
+
+
+@pytest.mark.parametrize("fit", ["rect", "quad"])
+def test_front_end_capacity(vk, fit):
+    """Five 16 x 16 squares (256 px, above the floor) and two slots: the count says five, both paths list labels 1 and 2."""
+    m = np.zeros((1, 48, 160), np.float32)
+    for i in range(5):
+        m[0, 16:32, 8 + 30 * i:24 + 30 * i] = 1.0
+    bare, rows, lists = _both_paths(vk, fit, torch.from_numpy(m).to(_dev()), 2, 0, bin_thresh=0.5, morph_kernel=1, open_iter=0, close_iter=0)
+    assert bare.counts.cpu().tolist() == [5] and bare.raw.shape[1] == 2
+    assert rows[0]["label"].tolist() == [1, 2] and rows[0]["area"].tolist() == [256, 256]
+    assert [d["label"] for d in lists[0]] == [1, 2]                                        # equal areas: the sort keeps label order
+
+
+def test_invalid_quad_record_is_in_records_not_in_the_list(vk):
+    case = next(c for c in GC.branch_cases() if c.name == "square2")                       # a 2 x 2 square: no quadrilateral fits
+    cfg = case.cfg
+    dets = vk.instances.detect(torch.from_numpy(case.probs()).to(_dev()), fit="quad", bin_thresh=cfg.thresh, min_area=cfg.min_area,
+                               morph_kernel=cfg.k, open_iter=cfg.oi, close_iter=cfg.ci, fit_outset_px=cfg.outset, max_components=cfg.cap,
+                               slots=False)
+    rows = dets.records()
+    assert len(rows) == 1 and rows[0]["valid"].tolist() == [0] and rows[0]["area"].tolist() == [4]
+    assert vk.geometry._quad_records(rows[0]) == []

@@ -12,15 +12,15 @@ touching ones as one, or put every diagonal 3 % long), so this module is the obj
     m = om.compute()                                          # one read-back
     m["pq"][0], m["mean_rel_d"][0], m["mean_hv_rel"][0]       # at IoU > 0.5
 
-``detect`` runs the geometry post-processing of ``vk.geometry`` and keeps everything on the device, with the label map as slots of
-the detection list; ``contingency`` counts the pixels of every (pred slot, GT slot) pair of two such results in one pass; ``match``
-pairs the objects (IoU > 1/2, which makes the pairing unique) and sums the statistics of the matched pairs at every IoU threshold.
+``detect`` (``vk.geometry.detect``, the same object) runs the geometry post-processing and keeps everything on the device, with the
+label map as slots of the detection list; ``contingency`` counts the pixels of every (pred slot, GT slot) pair of two such results
+in one pass; ``match`` pairs the objects (IoU > 1/2, which makes the pairing unique) and sums the statistics of the matched pairs at
+every IoU threshold.
 Integer counts and IEEE float64 in a fixed order: an epoch's totals do not depend on how it was cut into batches.  One foreground
 class per call, at most 256 objects per map and side.  CUDA tensors only: there is no CPU fallback."""
 from __future__ import annotations
 
-import ctypes as C
-from typing import Dict, List, Optional
+from typing import Dict, Optional
 
 import numpy as np
 import torch
@@ -28,6 +28,7 @@ import torch
 from . import _lib as L
 from . import geometry as G
 from ._lib import VkError
+from .geometry import Detections, detect
 
 __all__ = ["DEFAULT_IOU_THRESHOLDS", "GT_PRESET", "STATS_DTYPE", "Detections", "MatchResult", "ObjectMetrics", "detect", "detect_gt",
            "contingency", "match", "object_metrics", "summarize"]
@@ -37,18 +38,7 @@ MAX_THRESHOLDS = 16
 DEFAULT_IOU_THRESHOLDS = np.arange(0.5, 1.0, 0.05)             # float64: 0.5, 0.55, ... 0.95
 DEFAULT_IOU_THRESHOLDS.setflags(write=False)
 GT_PRESET = dict(bin_thresh=0.5, min_area=1, morph_kernel=1)    # a 0/1 mask as it is: no morphology, every component kept
-STATS_DTYPE = np.dtype([(f, "<i8") for f in L.INST_INT_FIELDS] + [(f, "<f8") for f in L.INST_FLOAT_FIELDS])
-assert STATS_DTYPE.itemsize == C.sizeof(L.vk_inst_stats)
-
-_FITS = {"rect": (L.vk_geom_det, np.dtype([("label", "<i4"), ("area", "<i4"), ("box", "<i4", (8,)), ("cx", "<f4"), ("cy", "<f4"),
-                                           ("rw", "<f4"), ("rh", "<f4"), ("ux", "<f4"), ("uy", "<f4"), ("hull_n", "<i4"),
-                                           ("reserved", "<i4"), ("d1", "<f8"), ("d2", "<f8"), ("d_mean", "<f8")])),
-         "quad": (L.vk_geom_quad, np.dtype([("label", "<i4"), ("area", "<i4"), ("box", "<i4", (8,)), ("cx", "<f4"), ("cy", "<f4"),
-                                            ("valid", "<i4"), ("branch", "<i4"), ("n_candidates", "<i4"), ("contour_n", "<i4"),
-                                            ("hull_n", "<i4"), ("flags", "<i4"), ("quality", "<f8"), ("d1", "<f8"), ("d2", "<f8"),
-                                            ("d_mean", "<f8")]))}
-for _ct, _dt in _FITS.values():
-    assert C.sizeof(_ct) == _dt.itemsize and _ct.d_mean.offset == _dt.fields["d_mean"][1]
+STATS_DTYPE = np.dtype(L.vk_inst_stats)
 
 
 def _iou_thresholds(thresholds) -> np.ndarray:
@@ -68,78 +58,6 @@ def _iou_thresholds(thresholds) -> np.ndarray:
     return thr
 
 
-class Detections:
-    """What one geometry call leaves, all on the device: ``clean`` uint8 [B, h, w] in {0, 255}; ``raw`` uint8 [B, max_components,
-    record bytes] (``vk_geom_det`` or ``vk_geom_quad`` records, slots in label order); ``counts`` int32 [B] (kept components, also
-    when they exceed ``max_components``); ``slots`` int32 [B, h, w]: the slot of every pixel's component, -1 for background and for
-    components below ``min_area``, -2 for a kept component beyond ``max_components``."""
-
-    def __init__(self, fit: str, clean: torch.Tensor, raw: torch.Tensor, counts: torch.Tensor, slots: torch.Tensor, max_components: int):
-        self.fit, self.clean, self.raw, self.counts, self.slots, self.max_components = fit, clean, raw, counts, slots, max_components
-
-    @property
-    def record_dtype(self) -> np.dtype:
-        return _FITS[self.fit][1]
-
-    @property
-    def diag_offset(self) -> int:
-        return int(_FITS[self.fit][0].d_mean.offset)
-
-    @property
-    def record_bytes(self) -> int:
-        return int(self.record_dtype.itemsize)
-
-    def records(self) -> List[np.ndarray]:
-        """Per map the structured records of its min(count, max_components) slots, in slot order.  The only method that reads back."""
-        host = self.raw.cpu().numpy().reshape(-1).view(self.record_dtype).reshape(self.raw.shape[0], self.max_components)
-        cnt = self.counts.cpu().numpy()
-        return [host[b, :min(int(cnt[b]), self.max_components)].copy() for b in range(host.shape[0])]
-
-
-def detect(prob: torch.Tensor, fit: str = "rect", bin_thresh: Optional[float] = None, min_area: Optional[int] = None,
-           morph_kernel: int = G.MORPH_KERNEL, open_iter: int = G.OPEN_ITER, close_iter: int = G.CLOSE_ITER,
-           fit_outset_px: int = G.FIT_OUTSET_PX, max_components: int = 64) -> Detections:
-    """``prob`` float32 [B, h, w] on the device -> ``Detections``; no host round trip.
-
-    ``fit``: "rect" (``vk_geom_minarearect``, bin_thresh 0.5 by default) or "quad" (``vk_geom_quadrilateral``, 0.45).  ``min_area`` in
-    pixels; None is the reference's max(200, int(0.0008 h w))."""
-    if fit not in _FITS:
-        raise ValueError("fit must be 'rect' or 'quad', got %r" % (fit,))
-    if not isinstance(prob, torch.Tensor) or prob.dim() != 3:
-        raise ValueError("expected a float32 tensor [B, h, w]")
-    if not prob.is_cuda:
-        raise VkError("probability maps are on %s: this package runs on an MI355X only and has no CPU fallback" % prob.device)
-    if not 1 <= int(max_components) <= 4096:
-        raise ValueError("max_components %r outside 1..4096" % (max_components,))
-    prob = prob.detach().contiguous().float()
-    B, h, w = (int(v) for v in prob.shape)
-    if bin_thresh is None:
-        bin_thresh = G.BIN_THRESH if fit == "rect" else G.BIN_THRESH_QUAD
-    if min_area is None:
-        min_area = max(200, int(G.MIN_AREA_FRAC * h * w))
-    cap = int(max_components)
-    desc = L.vk_geom_desc(h, w, float(bin_thresh), int(morph_kernel), int(open_iter), int(close_iter), int(min_area), cap)
-    lib = L.lib()
-    nbytes = lib.vk_geom_workspace_bytes(C.byref(desc), B)
-    if nbytes < 0:
-        L.check(-1, "vk_geom_workspace_bytes")
-    dev = prob.device
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    clean = torch.empty(B, h, w, dtype=torch.uint8, device=dev)
-    raw = torch.zeros(B, cap, C.sizeof(_FITS[fit][0]), dtype=torch.uint8, device=dev)
-    counts = torch.zeros(B, dtype=torch.int32, device=dev)
-    slots = torch.empty(B, h, w, dtype=torch.int32, device=dev)
-    st = L.current_stream()
-    if fit == "rect":
-        L.check(lib.vk_geom_minarearect(C.byref(desc), B, prob.data_ptr(), clean.data_ptr(), raw.data_ptr(), counts.data_ptr(),
-                                        ws.data_ptr(), nbytes, st), "vk_geom_minarearect")
-    else:
-        L.check(lib.vk_geom_quadrilateral(C.byref(desc), int(fit_outset_px), B, prob.data_ptr(), clean.data_ptr(), raw.data_ptr(),
-                                          counts.data_ptr(), ws.data_ptr(), nbytes, st), "vk_geom_quadrilateral")
-    L.check(lib.vk_geom_slot_map(C.byref(desc), B, ws.data_ptr(), nbytes, slots.data_ptr(), st), "vk_geom_slot_map")
-    return Detections(fit, clean, raw, counts, slots, cap)
-
-
 def detect_gt(mask: torch.Tensor, fit: str = "rect", fit_outset_px: int = G.FIT_OUTSET_PX, max_components: int = 64) -> Detections:
     """``detect`` with the ground-truth preset: a 0/1 mask [B, h, w] (any dtype) is taken as it is."""
     if isinstance(mask, torch.Tensor) and not mask.is_cuda:
@@ -150,6 +68,8 @@ def detect_gt(mask: torch.Tensor, fit: str = "rect", fit_outset_px: int = G.FIT_
 def _pair(pred: Detections, gt: Detections):
     if not isinstance(pred, Detections) or not isinstance(gt, Detections):
         raise ValueError("expected two Detections (vk.instances.detect)")
+    if pred.slots is None or gt.slots is None:
+        raise ValueError("matching needs the slot maps: these Detections were made with detect(slots=False)")
     if tuple(pred.slots.shape) != tuple(gt.slots.shape) or pred.slots.device != gt.slots.device:
         raise ValueError("prediction %s and ground truth %s differ in shape or device" % (tuple(pred.slots.shape), tuple(gt.slots.shape)))
     if pred.max_components > MAX_SLOTS or gt.max_components > MAX_SLOTS:
@@ -199,13 +119,13 @@ def _match_call(B, Mp, Mg, table, n_pred, n_gt, thr, dp, sp, dg, sg, totals, dev
     pair_gt = torch.empty(B, Mp, dtype=torch.int32, device=device)
     pair_iou = torch.empty(B, Mp, dtype=torch.float64, device=device)
     pair_derr = torch.empty(B, Mp, dtype=torch.float64, device=device)
-    per_image = torch.empty(B * k * rec // 8, dtype=torch.int64, device=device).view(torch.uint8).view(B, k, rec)
+    per_image = G._record_buffer((B, k), rec, device)
     acc = totals is not None
     if acc:
         if totals.dtype != torch.uint8 or tuple(totals.shape) != (k, rec) or not totals.is_contiguous() or totals.device != device:
             raise ValueError("totals must be the uint8 [%d, %d] tensor of an earlier match on %s" % (k, rec, device))
     else:
-        totals = torch.empty(k * rec // 8, dtype=torch.int64, device=device).view(torch.uint8).view(k, rec)
+        totals = G._record_buffer((k,), rec, device)
     L.check(L.lib().vk_inst_match(B, Mp, Mg, table.data_ptr(), n_pred.data_ptr(), n_gt.data_ptr(), k, thr.ctypes.data, dp, sp, dg, sg,
                                   pair_gt.data_ptr(), pair_iou.data_ptr(), pair_derr.data_ptr(), per_image.data_ptr(), totals.data_ptr(),
                                   1 if acc else 0, L.current_stream()), "vk_inst_match")
@@ -261,8 +181,7 @@ class ObjectMetrics:
 
     def __init__(self, fit: str = "rect", iou_thresholds=None, max_components: int = 64, fit_outset_px: int = G.FIT_OUTSET_PX,
                  refine: Optional[dict] = None, **pred_args):
-        if fit not in _FITS:
-            raise ValueError("fit must be 'rect' or 'quad', got %r" % (fit,))
+        G._fit(fit)
         if not 1 <= int(max_components) <= MAX_SLOTS:
             raise ValueError("max_components %r outside 1..%d" % (max_components, MAX_SLOTS))
         if refine is not None and not isinstance(refine, dict):

@@ -25,17 +25,13 @@ import torch
 
 from . import _lib as L
 from . import geometry as G
-from . import instances as I
 from . import prepost as PP
 from ._lib import VkError
 
 __all__ = ["FLAGS", "RECORD_DTYPE", "RefinedDetections", "corner_weights", "letterbox_affine", "params", "postprocess", "refine"]
 
 FLAGS = dict(L.SUBPIX_FLAGS)
-RECORD_DTYPE = np.dtype([("label", "<i4"), ("area", "<i4"), ("valid", "<i4"), ("reserved", "<i4"), ("flags", "<i4", (4,)),
-                         ("iters", "<i4", (4,)), ("v", "<f8", (8,)), ("vs", "<f8", (8,)), ("d1", "<f8"), ("d2", "<f8"), ("d_mean", "<f8")])
-assert RECORD_DTYPE.itemsize == C.sizeof(L.vk_subpix_quad) and RECORD_DTYPE.itemsize % 8 == 0
-assert RECORD_DTYPE.fields["d_mean"][1] == L.vk_subpix_quad.d_mean.offset
+RECORD_DTYPE = np.dtype(L.vk_subpix_quad)
 _METHODS = {"corner": L.VK_SUBPIX_CORNER, "lines": L.VK_SUBPIX_LINES}
 _CORNER_DEFAULTS = dict(win=5, zero_zone=-1, max_iter=40, eps=1e-3)
 _LINES_DEFAULTS = dict(lo=0.1, hi=0.5, n_stations=12, reach=6, level=None, max_shift=None)
@@ -80,12 +76,12 @@ def letterbox_affine(h: int, w: int, size: int, geometry="centered") -> np.ndarr
     return np.array([float(left), float(top), 1.0 / float(scale)], np.float64)
 
 
-class RefinedDetections(I.Detections):
+class RefinedDetections(G.Detections):
     """``Detections`` whose ``raw`` holds ``vk_subpix_quad`` records [B, max_components, 200] (``RECORD_DTYPE``): the refined vertices
     ``v`` (map coordinates) and ``vs`` (source coordinates), per-vertex ``flags`` and ``iters``, and the diagonals in source pixels.
     ``clean``, ``counts`` and ``slots`` are the source's own tensors, so it goes to ``vk.instances.match`` as it is."""
 
-    def __init__(self, source: I.Detections, raw: torch.Tensor, method: str):
+    def __init__(self, source: G.Detections, raw: torch.Tensor, method: str):
         super().__init__(source.fit, source.clean, raw, source.counts, source.slots, source.max_components)
         self.source, self.method = source, method
 
@@ -112,29 +108,28 @@ def _affine_tensor(affine, B: int, device) -> Optional[torch.Tensor]:
     return a.contiguous()
 
 
-def refine(dets: I.Detections, prob: torch.Tensor, method: str = "corner", affine=None, **kw) -> RefinedDetections:
+def refine(dets: G.Detections, prob: torch.Tensor, method: str = "corner", affine=None, **kw) -> RefinedDetections:
     """Refines the four corners of every record of ``dets`` on ``prob``, the float32 [B, h, w] map ``dets`` was detected on.  No host
     synchronisation.  ``affine``: None, (ox, oy, inv_scale) or one row per map (``letterbox_affine``); the diagonals and ``vs`` are then
     in source-image pixels.  Keyword parameters as in ``params``; ``level`` defaults to the fit's detection threshold."""
-    if not isinstance(dets, I.Detections) or isinstance(dets, RefinedDetections):
+    if not isinstance(dets, G.Detections) or isinstance(dets, RefinedDetections):
         raise ValueError("expected the Detections of vk.instances.detect")
+    if dets.slots is None:
+        raise ValueError("refinement needs the slot map: these Detections were made with detect(slots=False)")
     if not isinstance(prob, torch.Tensor) or prob.dim() != 3:
         raise ValueError("expected a float32 tensor [B, h, w]")
     if not prob.is_cuda or not dets.raw.is_cuda:
         raise VkError("probability maps are on %s: this package runs on an MI355X only and has no CPU fallback" % prob.device)
     if tuple(prob.shape) != tuple(dets.slots.shape) or prob.device != dets.raw.device:
         raise ValueError("the map %s is not the one the detections %s were made from" % (tuple(prob.shape), tuple(dets.slots.shape)))
-    p = params(method, G.BIN_THRESH if dets.fit == "rect" else G.BIN_THRESH_QUAD, **kw)
+    p = params(method, G._fit(dets.fit).bin_thresh, **kw)
     prob = prob.detach().contiguous().float()
     B, h, w = (int(v) for v in prob.shape)
-    ct = I._FITS[dets.fit][0]
-    rec = C.sizeof(L.vk_subpix_quad)
     aff = _affine_tensor(affine, B, prob.device)
-    out = torch.zeros(B * dets.max_components * rec // 8, dtype=torch.int64, device=prob.device).view(torch.uint8)
-    out = out.view(B, dets.max_components, rec)
-    L.check(L.lib().vk_subpix_refine(C.byref(p), B, h, w, prob.data_ptr(), dets.raw.data_ptr(), dets.record_bytes, ct.box.offset,
-                                     ct.valid.offset if dets.fit == "quad" else -1, dets.counts.data_ptr(), dets.max_components,
-                                     L.ptr(aff), out.data_ptr(), L.current_stream()), "vk_subpix_refine")
+    out = G._record_buffer((B, dets.max_components), RECORD_DTYPE.itemsize, prob.device, zero=True)
+    L.check(L.lib().vk_subpix_refine(C.byref(p), B, h, w, prob.data_ptr(), dets.raw.data_ptr(), dets.record_bytes, dets.box_offset,
+                                     dets.valid_offset, dets.counts.data_ptr(), dets.max_components, L.ptr(aff), out.data_ptr(),
+                                     L.current_stream()), "vk_subpix_refine")
     return RefinedDetections(dets, out, method)
 
 
@@ -144,21 +139,16 @@ def postprocess(prob: torch.Tensor, fit: str = "rect", method: str = "corner", a
     ``postprocess_minarearect_multi`` / ``postprocess_quadrilateral_multi``, sorted by area) with ``d1``, ``d2``, ``d_mean`` refined
     (source pixels when ``affine`` is given), ``box_subpix`` float64 [4, 2] (``vs``), ``box_subpix_map`` (``v``) and ``subpix_flags``
     [4] added; ``box`` stays the int32 fit.  ``detect_args`` go to ``vk.instances.detect``, ``refine_args`` to ``refine``."""
-    dets = I.detect(prob, fit=fit, **detect_args)
+    dets = G.detect(prob, fit=fit, **detect_args)
     fine = refine(dets, prob, method=method, affine=affine, **(refine_args or {}))
-    cap = dets.max_components
-    ct, to_dicts = (L.vk_geom_det, G._records) if fit == "rect" else (L.vk_geom_quad, G._quad_records)
-    src = (ct * (int(prob.shape[0]) * cap)).from_buffer_copy(dets.raw.cpu().numpy().tobytes())          # synchronises
+    counts = dets.counts.cpu().numpy()                    # synchronises; read once for both record lists
     out = []
-    for b, recs in enumerate(fine.records()):
-        rows = []
-        for s, r in enumerate(recs):
-            base = to_dicts(src[b * cap + s:b * cap + s + 1], 1, 1)
-            if not base:                                  # a quadrilateral record with valid == 0: absent from the reference's list
-                continue
-            base[0].update(d1=float(r["d1"]), d2=float(r["d2"]), d_mean=float(r["d_mean"]), box_subpix=r["vs"].reshape(4, 2).copy(),
-                           box_subpix_map=r["v"].reshape(4, 2).copy(), subpix_flags=r["flags"].copy())
-            rows.append(base[0])
-        rows.sort(key=lambda d: d["area"], reverse=True)
+    for coarse, recs in zip(dets.records(counts), fine.records(counts)):
+        by_label = dict(zip(recs["label"].tolist(), recs))          # a refined record carries its source's label, unique within a map
+        rows = G._fit(fit).to_dicts(coarse)               # sorted by area; without the quadrilateral records of valid == 0
+        for d in rows:
+            r = by_label[d["label"]]
+            d.update(d1=float(r["d1"]), d2=float(r["d2"]), d_mean=float(r["d_mean"]), box_subpix=r["vs"].reshape(4, 2).copy(),
+                     box_subpix_map=r["v"].reshape(4, 2).copy(), subpix_flags=r["flags"].copy())
         out.append(rows)
     return dets.clean, out

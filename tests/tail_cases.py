@@ -439,7 +439,7 @@ def adamw_ref(p, g, m, v, hp, t, factor):
 
 
 def adamw_bounds(p, g, m, v, hp, t, factor):
-    """Elementwise bounds of (p', m', v') against adamw_ref, counted along k_adamw / k_adamw_dev / adamw_elem WITHOUT contraction (a fused
+    """Elementwise bounds of (p', m', v') against adamw_ref, counted along adamw_elem (csrc/optim.hip) WITHOUT contraction (a fused
     multiply-add rounds once where this counts twice); sqrtf and / are correctly rounded under csrc/Makefile's flags.  u = 2^-24.
         gi = g * factor                              1 rounding, and factor itself (inv_scale / grad_scale to fp32): 2 u |gi|
         d = gi - m; e = d * (1 - beta1); m' = m + e  (1 - beta1) in fp32 is 1 more: (1 - beta1)(2 u |gi| + u |d|) + 2 u |e| + u |m'|

@@ -165,7 +165,7 @@ def test_adamw_reference_equals_torch_adamw_in_float64(hp, t0):
 
 @pytest.mark.parametrize("zero_grad", [False, True])
 def test_adamw_exact_tier_every_intermediate_is_an_fp32_number(zero_grad):
-    """The chain of k_adamw in float64, with and without the gradient factor: each intermediate survives a round trip through fp32, so
+    """The chain of adamw_elem in float64, with and without the gradient factor: each intermediate survives a round trip through fp32, so
     fp32 arithmetic forms it without rounding in any association and with or without fused multiply-adds."""
     n = 100003
     hp = dict(TC.EXACT_HP, eps=2.0 ** -20) if zero_grad else TC.EXACT_HP

@@ -673,7 +673,7 @@ def test_adamw_segments_ragged_lengths_gaps_and_counters():
 
 
 def test_adamw_300_single_chunk_segments():
-    """More segments than the 256 threads of k_adamw_prepare_segments: its loop takes a second trip."""
+    """More segments than the 256 threads of k_adamw_prepare: its loop takes a second trip."""
     lengths = [1 + (i * 37) % 61 for i in range(300)]
     ranges, total = TC.ragged_segments(lengths)
     perm = [(i * 7) % 300 for i in range(300)]                            # 7 is coprime to 300: a permutation
@@ -684,8 +684,11 @@ def test_adamw_300_single_chunk_segments():
 
 
 def test_adamw_segments_equal_the_whole_buffer_kernel_at_2e20():
-    """n = 2^20 + 3 (past the 1,048,576-thread cap of the whole-buffer kernel) cut into ragged adjacent segments with equal counters:
-    the two entry points agree bit for bit on p, exp_avg and exp_avg_sq."""
+    """n = 2^20 + 3 (past the 1,048,576-thread cap of the whole-buffer kernel, whose loop takes a second trip) cut into ragged adjacent
+    segments with equal counters: the four entry points (vk_adamw_step, vk_adamw_step_amp, vk_adamw_step_amp_segments, vk_adamw_step_groups
+    with one group and no coefficient) agree bit for bit on p, exp_avg and exp_avg_sq over two steps from the same state at the same step
+    number with the same factor 2^-11, and the bf16 copies of the two whole-buffer entries agree.  Every entry runs one element
+    function; this is the test that ties the grid-stride loop of the whole-buffer kernel to the block-table loop of the per-tensor one."""
     n = 2 ** 20 + 3
     g = torch.Generator().manual_seed(23)
     p0, m0, v0 = torch.randn(n, generator=g), torch.randn(n, generator=g) * 0.01, torch.rand(n, generator=g) * 1e-3
@@ -693,23 +696,36 @@ def test_adamw_segments_equal_the_whole_buffer_kernel_at_2e20():
     cuts = [0, 1, 3, 258, 4354, 8450, 12547, 300000, 300001, 777777, n - 4097, n - 1, n]
     segs = [(cuts[i], cuts[i + 1], i) for i in range(len(cuts) - 1)]
     seg, blocks, nb = seg_tables(segs)
-    A = [guarded(t) for t in (p0, gr, m0, v0)]
-    B = [guarded(t) for t in (p0, gr, m0, v0)]
-    step_a = torch.full((1,), 4, dtype=torch.int32, device=dev())
-    steps_b = torch.full((len(segs),), 4, dtype=torch.int32, device=dev())
-    scr_a, scr_b = torch.zeros(4, device=dev()), torch.zeros(4 + 2 * len(segs), device=dev())
+    hyper = (5e-5, 0.9, 0.999, 1e-8, 1e-4)
+    names = ("step", "amp", "segments", "groups")
+    S = {e: [guarded(t) for t in (p0, gr, m0, v0)] for e in names}
+    ptrs = {e: [v.data_ptr() for _, v in S[e]] for e in names}
+    LP = {e: guarded(torch.full((n,), SENTINEL).to(torch.bfloat16)) for e in ("step", "amp")}
+    step_amp = torch.full((1,), 4, dtype=torch.int32, device=dev())
+    steps = {e: torch.full((len(segs),), 4, dtype=torch.int32, device=dev()) for e in ("segments", "groups")}
+    scr_amp = torch.zeros(4, device=dev())
+    scr = {e: torch.zeros(4 + 2 * len(segs), device=dev()) for e in ("segments", "groups")}
     gs = torch.full((1,), 1024.0, device=dev())
-    for _ in range(2):
-        L_.check(lib().vk_adamw_step_amp(n, *[v.data_ptr() for _, v in A], 5e-5, 0.9, 0.999, 1e-8, 1e-4, step_a.data_ptr(), 0.5, gs.data_ptr(), None,
-                                         scr_a.data_ptr(), None, 0, st()))
-        L_.check(lib().vk_adamw_step_amp_segments(len(segs), seg.data_ptr(), nb, blocks.data_ptr(), *[v.data_ptr() for _, v in B], 5e-5, 0.9, 0.999,
-                                                  1e-8, 1e-4, steps_b.data_ptr(), 0.5, gs.data_ptr(), None, scr_b.data_ptr(), st()))
+    seg_group = torch.zeros(len(segs), dtype=torch.int32, device=dev())
+    groups = (L_.vk_adamw_group * 1)(L_.vk_adamw_group(*hyper))
+    for k in range(2):
+        L_.check(lib().vk_adamw_step(n, *ptrs["step"], *hyper, 5 + k, 2.0 ** -11, None, LP["step"][1].data_ptr(), L_.VK_BF16, st()))
+        L_.check(lib().vk_adamw_step_amp(n, *ptrs["amp"], *hyper, step_amp.data_ptr(), 0.5, gs.data_ptr(), None, scr_amp.data_ptr(),
+                                         LP["amp"][1].data_ptr(), L_.VK_BF16, st()))
+        L_.check(lib().vk_adamw_step_amp_segments(len(segs), seg.data_ptr(), nb, blocks.data_ptr(), *ptrs["segments"], *hyper,
+                                                  steps["segments"].data_ptr(), 0.5, gs.data_ptr(), None, scr["segments"].data_ptr(), st()))
+        L_.check(lib().vk_adamw_step_groups(len(segs), seg.data_ptr(), seg_group.data_ptr(), nb, blocks.data_ptr(), *ptrs["groups"], 1, groups,
+                                            steps["groups"].data_ptr(), 0.5, gs.data_ptr(), None, None, scr["groups"].data_ptr(), st()))
         torch.cuda.synchronize()
-        for nm, (fa, va), (fb, vb) in zip(("p", "grad", "exp_avg", "exp_avg_sq"), A, B):
-            assert guards_ok(fa) and guards_ok(fb)
-            assert torch.equal(va, vb), f"{nm}: " + first_bad(vb, va)
-    assert step_a.item() == 6 and steps_b.tolist() == [6] * len(segs)
-    assert not torch.equal(A[0][1].cpu(), p0)
+        for e in names:
+            for nm, (fa, va), (fb, vb) in zip(("p", "grad", "exp_avg", "exp_avg_sq"), S["amp"], S[e]):
+                assert guards_ok(fb), f"{e}: {nm} written outside [0, n)"
+                assert torch.equal(va, vb), f"step {k}: {e} against amp: {nm}: " + first_bad(vb, va)
+        assert guards_ok(LP["step"][0]) and guards_ok(LP["amp"][0])
+        assert torch.equal(LP["step"][1], LP["amp"][1]), f"step {k}: bf16 copy: " + first_bad(LP["step"][1].float(), LP["amp"][1].float())
+        assert torch.equal(LP["amp"][1], S["amp"][0][1].to(torch.bfloat16))
+    assert step_amp.item() == 6 and steps["segments"].tolist() == [6] * len(segs) and steps["groups"].tolist() == [6] * len(segs)
+    assert not torch.equal(S["amp"][0][1].cpu(), p0)
 
 
 # ================================================================================================ GradScaler kernels

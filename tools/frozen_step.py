@@ -16,7 +16,7 @@ model = vk.Unet(encoder_weights=None).to(dev).train()
 x = torch.randn(32, 3, 512, 512, device=dev)
 y = (torch.rand(32, 1, 512, 512, device=dev) > 0.7).float()
 opt_full = vk.adamw_for(model, lr=5e-5, weight_decay=1e-4)                            # whole-buffer kernel, one counter
-opt_frozen = vk.FusedAdamW(model.parameters(), lr=5e-5, weight_decay=1e-4).attach(model)   # segmented kernel
+opt_frozen = vk.FusedAdamW(model.parameters(), lr=5e-5, weight_decay=1e-4).attach(model)   # per-tensor kernel
 n_dec = sum(p.numel() for n, p in model.named_parameters() if not n.startswith("encoder."))
 print(f"params {sum(p.numel() for p in model.parameters())}, decoder+head {n_dec}")
 

@@ -4,7 +4,9 @@ loss_and_backward + (clip) + FusedAdamW.step, event-timed, alternating rounds.
   (b) three groups (encoder at 0.2 lr / decoder + head / no-decay 1-D tensors)   vk_adamw_step_groups
   (c) (b) + optimizer.clip_grad_norm_(max_norm)                     vk_grad_norm_segments, coefficient folded into the step
   (d) (a) + torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm)   what worked before: foreach kernels over 140 views
-Also the clip call and the optimizer step alone.  `--trace`: a few steps of (c) only, for a rocprofv3 --kernel-trace --stats run of its own."""
+  (e) (a) with the encoder frozen                                   one group over a partial set: vk_adamw_step_groups, group table of zeros
+Also the clip call and the optimizer step alone.  `--trace [letters]`: a few steps of each listed round only ((c) when none is given), for
+a rocprofv3 --kernel-trace --stats run of its own."""
 import importlib
 import sys
 from pathlib import Path
@@ -32,11 +34,17 @@ def three_groups():
 opts = {"a": vk.adamw_for(model, lr=LR, weight_decay=WD),
         "b": vk.adamw_for(model, lr=LR, weight_decay=WD, groups=three_groups()),
         "c": vk.adamw_for(model, lr=LR, weight_decay=WD, groups=three_groups()),
-        "d": vk.adamw_for(model, lr=LR, weight_decay=WD)}
-NAMES = {"a": "default", "b": "three groups", "c": "three groups + clip_grad_norm_", "d": "default + torch clip_grad_norm_"}
+        "d": vk.adamw_for(model, lr=LR, weight_decay=WD),
+        "e": vk.adamw_for(model, lr=LR, weight_decay=WD)}
+NAMES = {"a": "default", "b": "three groups", "c": "three groups + clip_grad_norm_", "d": "default + torch clip_grad_norm_",
+         "e": "default, frozen encoder"}
 params = list(model.parameters())
 print(f"params {sum(p.numel() for p in params)} in {len(params)} tensors, flat buffer {model.flat_grads.numel() * 4 / 1e6:.1f} MB, "
       f"groups {[len(g['params']) for g in opts['b'].param_groups]}")
+
+
+def select(k):
+    model.encoder.requires_grad_(k != "e")       # outside the timed region
 
 
 def step(k):
@@ -64,15 +72,20 @@ def timed(fn, steps, warm):
 
 
 if "--trace" in sys.argv:
-    for _ in range(6):
-        step("c")
+    at = sys.argv.index("--trace") + 1
+    which = sys.argv[at] if at < len(sys.argv) else "c"
+    for k in which:
+        select(k)
+        for _ in range(6):
+            step(k)
     torch.cuda.synchronize()
-    print("trace run done: 6 steps of (c)")
+    print(f"trace run done: 6 steps of each of ({which})")
     sys.exit(0)
 
 res = {k: [] for k in opts}
 for rnd in range(4):
     for k in opts:
+        select(k)
         ms = timed(lambda: step(k), 10, 3)
         res[k].append(ms)
         print(f"round {rnd} ({k}) {NAMES[k]:32s} {ms:8.3f} ms/step", flush=True)
@@ -82,17 +95,20 @@ for k in opts:
 print(f"(b) - (a) = {med['b'] - med['a']:+.3f} ms   (c) - (b) = {med['c'] - med['b']:+.3f} ms   (d) - (a) = {med['d'] - med['a']:+.3f} ms   "
       f"(c) - (d) = {med['c'] - med['d']:+.3f} ms")
 
+select("a")
 # the pieces alone, back to back on a gradient buffer left by one backward (so it is as cache-resident as 98 MB can be)
 step("c")
 torch.cuda.synchronize()
 print(f"optimizer.clip_grad_norm_ alone:            {timed(lambda: opts['c'].clip_grad_norm_(MAX_NORM), 50, 5):.4f} ms (two launches)")
 print(f"torch.nn.utils.clip_grad_norm_ alone:       {timed(lambda: torch.nn.utils.clip_grad_norm_(params, MAX_NORM), 20, 3):.4f} ms")
-for k in ("a", "b"):
+for k in ("a", "b", "e"):
+    select(k)
     step(k)
     print(f"optimizer.step() alone, ({k}) {NAMES[k]:14s} {timed(opts[k].step, 50, 5):.4f} ms (prepare + update launches)")
 
 L = vk.lib()
-for k in ("a", "c"):
+for k in ("a", "c", "e"):
+    select(k)
     step(k)
     torch.cuda.synchronize()
     vk._lib.prof_collect()

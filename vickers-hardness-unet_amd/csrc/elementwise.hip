@@ -2,20 +2,13 @@
 // tensors are NHWC and are moved as 16-byte vectors; per-channel reductions use wave shuffles + LDS
 // and finish with two fp64 atomics per channel per workgroup.
 // Reference operators replaced (all dispatched by reference train.py:436 model(x) / :438 loss /
-// :443,:448 backward / :449 optimizer.step): batch_norm, relu, max_pool2d, add, interpolate(nearest),
-// cat, BCEWithLogitsLoss, smp DiceLoss, AdamW.
+// :443,:448 backward): batch_norm, relu, max_pool2d, add, interpolate(nearest), cat, BCEWithLogitsLoss,
+// smp DiceLoss.  The optimizer (:449) is optim.hip.
 #include <math.h>
 
 #include "vk_common.h"
 
 namespace vk {
-
-static inline int grid_for(size_t work_items, int block = 256, int max_blocks = 256 * 16) {
-  size_t b = (work_items + block - 1) / block;
-  if (b > (size_t)max_blocks) b = max_blocks;
-  if (b < 1) b = 1;
-  return (int)b;
-}
 
 // Channel-group invariant of the flat per-channel passes (k_bn_add_relu, k_bn_bwd_apply): a thread fixes its channel group once and
 // then walks a grid-stride loop, which keeps that group only if grid * 256 is a multiple of the CV = C / VE vectors of a pixel.  So the
@@ -1223,134 +1216,6 @@ __global__ void k_loss_bwd(size_t count, const float* __restrict__ x, const floa
   }
 }
 
-// ------------------------------------------------------------------------------------------------
-// K15: AdamW over the flat fp32 buffers (same arithmetic order as torch/optim/adam.py single-tensor path)
-template <typename LT>
-__global__ void k_adamw(size_t n, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                        float lr, float beta1, float beta2, float eps, float wd, float step_size, float bc2_sqrt,
-                        float inv_scale, const int* found_inf, LT* lowp) {
-  if (found_inf && *found_inf) return;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const float gi = g[i] * inv_scale;
-    float pi = p[i] * (1.f - lr * wd);
-    float mi = m[i];
-    mi = mi + (gi - mi) * (1.f - beta1);
-    const float vi = v[i] * beta2 + (1.f - beta2) * gi * gi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    pi = pi - step_size * (mi / denom);
-    p[i] = pi;
-    m[i] = mi;
-    v[i] = vi;
-    if (lowp) st1(lowp + i, pi);
-  }
-}
-
-__global__ void k_check_inf(size_t n, const float* __restrict__ g, int* found) {
-  bool bad = false;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-    bad |= !isfinite(g[i]);
-  if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(found, 1);
-}
-
-// K16, GradScaler form (torch._amp_foreach_non_finite_check_and_unscale_ over the ONE flat gradient buffer):
-// g *= *inv_scale (skipped when the factor is exactly 1: GradScaler's check-only call passes a dummy 1.0), *found_inf = 1.0f if any
-// element is inf / nan.  16-byte accesses; n4 = n / 4 (the flat buffer is padded to a multiple of 64 elements).
-__global__ __launch_bounds__(256) void k_amp_unscale_check(size_t n4, float* __restrict__ g, const float* __restrict__ inv_scale,
-                                                           float* __restrict__ found_inf) {
-  const float inv = inv_scale ? *inv_scale : 1.f;
-  const bool scale = inv != 1.f;
-  bool bad = false;
-  f32x4_t* g4 = reinterpret_cast<f32x4_t*>(g);
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
-    f32x4_t v = g4[i];
-    bad |= !(isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2]) && isfinite(v[3]));
-    if (scale) {
-      v = v * inv;
-      g4[i] = v;
-    }
-  }
-  if (__any(bad) && (threadIdx.x & 63) == 0) *found_inf = 1.f;     // every writer stores the same value
-}
-
-// One thread: resolves the GradScaler protocol on the device for k_adamw_dev (no host round trip, train.py:443-445).
-//   st[0] = skip flag (found_inf != 0), st[1] = lr / (1 - beta1^t), st[2] = sqrt(1 - beta2^t), st[3] = inv_scale / grad_scale;
-//   the step counter t advances only when the step is taken (torch: optimizer.step() is not called on an overflow).
-__global__ void k_adamw_prepare(int* __restrict__ step_count, const float* __restrict__ grad_scale, const float* __restrict__ found_inf,
-                                float lr, float beta1, float beta2, float inv_scale, float* __restrict__ st) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  const bool skip = found_inf && *found_inf != 0.f;
-  int t = *step_count;
-  if (!skip) {
-    t += 1;
-    *step_count = t;
-  }
-  const double bc1 = 1.0 - pow((double)beta1, (double)(t > 0 ? t : 1));
-  const double bc2 = 1.0 - pow((double)beta2, (double)(t > 0 ? t : 1));
-  st[0] = skip ? 1.f : 0.f;
-  st[1] = (float)((double)lr / bc1);
-  st[2] = (float)sqrt(bc2);
-  st[3] = grad_scale ? (float)((double)inv_scale / (double)*grad_scale) : inv_scale;
-}
-
-// adamw_elem (one element of k_adamw_segments, bit for bit k_adamw_dev's loop body) lives in vk_common.h: optim_groups.hip shares it.
-template <typename LT>
-__global__ void k_adamw_dev(size_t n, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                            float lr, float beta1, float beta2, float eps, float wd, const float* __restrict__ st, LT* lowp) {
-  if (st[0] != 0.f) return;
-  const float step_size = st[1], bc2_sqrt = st[2], inv_scale = st[3];
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const float gi = g[i] * inv_scale;
-    float pi = p[i] * (1.f - lr * wd);
-    float mi = m[i];
-    mi = mi + (gi - mi) * (1.f - beta1);
-    const float vi = v[i] * beta2 + (1.f - beta2) * gi * gi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    pi = pi - step_size * (mi / denom);
-    p[i] = pi;
-    m[i] = mi;
-    v[i] = vi;
-    if (lowp) st1(lowp + i, pi);
-  }
-}
-
-// Per-tensor AdamW (vk_adamw_step_amp_segments).  Prepare: k_adamw_prepare once per segment — its tensor's counter advances unless
-// the step is skipped, and st[4 + 2s], st[5 + 2s] = lr / (1 - beta1^t), sqrt(1 - beta2^t) of that counter; st[0], st[3] as there.
-__global__ __launch_bounds__(256) void k_adamw_prepare_segments(int nseg, const int64_t* __restrict__ seg, int* __restrict__ steps,
-                                                                const float* __restrict__ grad_scale, const float* __restrict__ found_inf,
-                                                                float lr, float beta1, float beta2, float inv_scale, float* __restrict__ st) {
-  const bool skip = found_inf && *found_inf != 0.f;
-  if (threadIdx.x == 0) {
-    st[0] = skip ? 1.f : 0.f;
-    st[1] = st[2] = 0.f;
-    st[3] = grad_scale ? (float)((double)inv_scale / (double)*grad_scale) : inv_scale;
-  }
-  for (int s = threadIdx.x; s < nseg; s += blockDim.x) {
-    int* const cnt = steps + seg[3 * (size_t)s + 2];
-    int t = *cnt;
-    if (!skip) {
-      t += 1;
-      *cnt = t;
-    }
-    const double bc1 = 1.0 - pow((double)beta1, (double)(t > 0 ? t : 1));
-    const double bc2 = 1.0 - pow((double)beta2, (double)(t > 0 ? t : 1));
-    st[4 + 2 * s] = (float)((double)lr / bc1);
-    st[5 + 2 * s] = (float)sqrt(bc2);
-  }
-}
-
-// Update: workgroup b owns chunk blocks[b].y of segment blocks[b].x (a table built once per set of segments: no search per element)
-__global__ __launch_bounds__(256) void k_adamw_segments(const int64_t* __restrict__ seg, const int2* __restrict__ blocks, float* __restrict__ p,
-                                                        const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, float lr,
-                                                        float beta1, float beta2, float eps, float wd, const float* __restrict__ st) {
-  if (st[0] != 0.f) return;
-  const int2 b = blocks[blockIdx.x];
-  const int64_t begin = seg[3 * (size_t)b.x] + (int64_t)b.y * VK_ADAMW_SEGMENT_CHUNK;
-  const int64_t end = min(begin + (int64_t)VK_ADAMW_SEGMENT_CHUNK, seg[3 * (size_t)b.x + 1]);
-  const float step_size = st[4 + 2 * b.x], bc2_sqrt = st[5 + 2 * b.x], inv_scale = st[3];
-  for (int64_t i = begin + threadIdx.x; i < end; i += blockDim.x)
-    (void)adamw_elem((size_t)i, p, g, m, v, lr, beta1, beta2, eps, wd, step_size, bc2_sqrt, inv_scale);
-}
-
 }  // namespace vk
 
 // =================================================================================================
@@ -1686,104 +1551,6 @@ extern "C" int vk_bce_dice_loss(size_t count, const float* logits, const float* 
   hipLaunchKernelGGL(k_loss_reduce, dim3(grid_for(vec_ok ? (count + 3) / 4 : count, 256, 2048)), dim3(256), 0, st, count, logits, target, sums, vec_ok);
   hipLaunchKernelGGL(k_loss_finalize, dim3(1), dim3(64), 0, st, (double)count, sums, loss_out, w_bce, w_dice);
   if (dlogits) hipLaunchKernelGGL(k_loss_bwd, dim3(grid_for(count)), dim3(256), 0, st, count, logits, target, sums, grad_scale, dlogits);
-  VK_CHECK_HIP(hipGetLastError());
-  return VK_OK;
-}
-
-extern "C" int vk_adamw_step(size_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
-                             float beta2, float eps, float weight_decay, int step, float inv_scale, const int* found_inf,
-                             void* lowp_copy, vk_dtype lowp_dtype, void* stream) {
-  VK_CHECK_ARG(n > 0 && param && grad && exp_avg && exp_avg_sq && step >= 1, "vk_adamw_step: bad argument");
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  const float step_size = (float)((double)lr / bc1);
-  const float bc2_sqrt = (float)sqrt(bc2);
-  hipStream_t st = (hipStream_t)stream;
-  vkh::ProfScope ps_("adamw", st, 0.0, (double)n * 28.0);
-  dim3 grid(grid_for(n)), block(256);
-  if (!lowp_copy || lowp_dtype == VK_F32) {
-    hipLaunchKernelGGL(k_adamw<float>, grid, block, 0, st, n, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay,
-                       step_size, bc2_sqrt, inv_scale, found_inf, (float*)nullptr);
-  } else if (lowp_dtype == VK_BF16) {
-    hipLaunchKernelGGL(k_adamw<bf16_t>, grid, block, 0, st, n, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay,
-                       step_size, bc2_sqrt, inv_scale, found_inf, (bf16_t*)lowp_copy);
-  } else {
-    hipLaunchKernelGGL(k_adamw<f16_t>, grid, block, 0, st, n, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay,
-                       step_size, bc2_sqrt, inv_scale, found_inf, (f16_t*)lowp_copy);
-  }
-  VK_CHECK_HIP(hipGetLastError());
-  return VK_OK;
-}
-
-extern "C" int vk_adamw_step_amp(size_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
-                                 float beta2, float eps, float weight_decay, int* step_count, float inv_scale, const float* grad_scale,
-                                 const float* found_inf, float* scratch4, void* lowp_copy, vk_dtype lowp_dtype, void* stream) {
-  VK_CHECK_ARG(n > 0 && param && grad && exp_avg && exp_avg_sq && step_count && scratch4, "vk_adamw_step_amp: bad argument");
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_adamw_prepare, dim3(1), dim3(64), 0, st, step_count, grad_scale, found_inf, lr, beta1, beta2, inv_scale, scratch4);
-  vkh::ProfScope ps_("adamw", st, 0.0, (double)n * 28.0);
-  dim3 grid(grid_for(n)), block(256);
-  if (!lowp_copy || lowp_dtype == VK_F32) {
-    hipLaunchKernelGGL(k_adamw_dev<float>, grid, block, 0, st, n, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay,
-                       (const float*)scratch4, (float*)nullptr);
-  } else if (lowp_dtype == VK_BF16) {
-    hipLaunchKernelGGL(k_adamw_dev<bf16_t>, grid, block, 0, st, n, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay,
-                       (const float*)scratch4, (bf16_t*)lowp_copy);
-  } else {
-    hipLaunchKernelGGL(k_adamw_dev<f16_t>, grid, block, 0, st, n, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay,
-                       (const float*)scratch4, (f16_t*)lowp_copy);
-  }
-  VK_CHECK_HIP(hipGetLastError());
-  return VK_OK;
-}
-
-extern "C" int vk_adamw_segment_blocks(int n_segments, const int64_t* seg, int32_t* blocks, int capacity) {
-  VK_CHECK_ARG(n_segments >= 1 && seg && (capacity >= 0), "vk_adamw_segment_blocks: bad argument");
-  int64_t rows = 0;
-  for (int s = 0; s < n_segments; ++s) {
-    const int64_t b = seg[3 * s], e = seg[3 * s + 1];
-    VK_CHECK_ARG(0 <= b && b < e && seg[3 * s + 2] >= 0, "vk_adamw_segment_blocks: bad segment %d [%lld, %lld)", s, (long long)b, (long long)e);
-    const int64_t chunks = (e - b + VK_ADAMW_SEGMENT_CHUNK - 1) / VK_ADAMW_SEGMENT_CHUNK;
-    for (int64_t c = 0; c < chunks; ++c, ++rows) {
-      VK_CHECK_ARG(rows < (1 << 30), "vk_adamw_segment_blocks: too many blocks");
-      if (blocks && rows < capacity) {
-        blocks[2 * rows] = s;
-        blocks[2 * rows + 1] = (int32_t)c;
-      }
-    }
-  }
-  VK_CHECK_ARG(!blocks || rows <= capacity, "vk_adamw_segment_blocks: %lld rows do not fit in %d", (long long)rows, capacity);
-  return (int)rows;
-}
-
-extern "C" int vk_adamw_step_amp_segments(int n_segments, const int64_t* segments, int n_blocks, const int32_t* blocks, float* param,
-                                          const float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2, float eps,
-                                          float weight_decay, int* step_counts, float inv_scale, const float* grad_scale,
-                                          const float* found_inf, float* scratch, void* stream) {
-  VK_CHECK_ARG(n_segments >= 1 && n_blocks >= 1 && segments && blocks && param && grad && exp_avg && exp_avg_sq && step_counts && scratch,
-               "vk_adamw_step_amp_segments: bad argument");
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_adamw_prepare_segments, dim3(1), dim3(256), 0, st, n_segments, segments, step_counts, grad_scale, found_inf, lr, beta1,
-                     beta2, inv_scale, scratch);
-  vkh::ProfScope ps_("adamw_segments", st, 0.0, (double)n_blocks * VK_ADAMW_SEGMENT_CHUNK * 28.0);
-  hipLaunchKernelGGL(k_adamw_segments, dim3((unsigned)n_blocks), dim3(256), 0, st, segments, (const int2*)blocks, param, grad, exp_avg, exp_avg_sq,
-                     lr, beta1, beta2, eps, weight_decay, (const float*)scratch);
-  VK_CHECK_HIP(hipGetLastError());
-  return VK_OK;
-}
-
-extern "C" int vk_amp_unscale_check(size_t n, float* grad, const float* inv_scale, float* found_inf, void* stream) {
-  VK_CHECK_ARG(n > 0 && grad && found_inf, "vk_amp_unscale_check: null argument");
-  VK_CHECK_ARG((n & 3) == 0 && ((uintptr_t)grad & 15) == 0, "vk_amp_unscale_check: the gradient buffer must be 16-byte aligned with n %% 4 == 0");
-  vkh::ProfScope ps_("amp_unscale_check", (hipStream_t)stream, 0.0, (double)n * 4.0);
-  hipLaunchKernelGGL(k_amp_unscale_check, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, n / 4, grad, inv_scale, found_inf);
-  VK_CHECK_HIP(hipGetLastError());
-  return VK_OK;
-}
-
-extern "C" int vk_amp_check_inf(size_t n, const float* grad, int* found_inf, void* stream) {
-  VK_CHECK_ARG(n > 0 && grad && found_inf, "vk_amp_check_inf: null argument");
-  hipLaunchKernelGGL(k_check_inf, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, n, grad, found_inf);
   VK_CHECK_HIP(hipGetLastError());
   return VK_OK;
 }

@@ -286,27 +286,12 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   return v;
 }
 
-// ---------------------------------------------------------------- AdamW element shared by elementwise.hip and optim_groups.hip
-// one element of k_adamw_segments: k_adamw_dev's expression with its fused multiply-adds spelled out and contraction off.  They are
-// exactly the ones the compiler forms in k_adamw_dev's loop (g*inv - m, m + d*(1 - beta1), gi*((1 - beta2)*gi) + v*beta2,
-// p*(1 - lr*wd) - step*ratio); written as plain source the vectoriser pairs this loop's products into v_pk_mul_f32 instead and
-// rounds them separately.  So the two kernels agree bit for bit (tests/test_frozen_params_gpu.py holds them to it).
-__device__ __forceinline__ float adamw_elem(size_t i, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                            float* __restrict__ v, float lr, float beta1, float beta2, float eps, float wd, float step_size,
-                                            float bc2_sqrt, float inv_scale) {
-#pragma clang fp contract(off)
-  const float gr = g[i];
-  const float gi = gr * inv_scale;
-  const float keep = __builtin_fmaf(-lr, wd, 1.f);                                  // 1 - lr*wd
-  float mi = m[i];
-  mi = __builtin_fmaf(__builtin_fmaf(gr, inv_scale, -mi), 1.f - beta1, mi);        // m + (gi - m)*(1 - beta1)
-  const float vi = __builtin_fmaf(gi, (1.f - beta2) * gi, v[i] * beta2);          // v*beta2 + (1 - beta2)*gi*gi
-  const float denom = sqrtf(vi) / bc2_sqrt + eps;
-  const float pi = __builtin_fmaf(p[i], keep, -(step_size * (mi / denom)));        // p*(1 - lr*wd) - step*(m / denom)
-  p[i] = pi;
-  m[i] = mi;
-  v[i] = vi;
-  return pi;
+// ---------------------------------------------------------------- grid of a grid-stride loop (host; elementwise.hip, optim.hip)
+static inline int grid_for(size_t work_items, int block = 256, int max_blocks = 256 * 16) {
+  size_t b = (work_items + block - 1) / block;
+  if (b > (size_t)max_blocks) b = max_blocks;
+  if (b < 1) b = 1;
+  return (int)b;
 }
 
 }  // namespace vk

@@ -15,8 +15,8 @@ foreach inf check over the 140 gradient views by one pass over the flat buffer.
 
 Fine-tuning (frozen tensors, or an optimizer over a subset of the model's parameters): like torch, a step updates only the owned
 tensors that have a gradient, and each tensor keeps its own step count (torch's per-parameter ``state["step"]``), so a tensor that
-is unfrozen later starts its bias correction at step 1.  That is ``vk_adamw_step_amp_segments``: one segment per tensor, its tables
-built once per set of tensors.  As long as every step has covered every tensor, the whole-buffer kernel and its one counter run.
+is unfrozen later starts its bias correction at step 1.  That is the per-tensor step: one segment per tensor, its tables built once
+per set of tensors.  As long as every step has covered every tensor, the whole-buffer kernel and its one counter run.
 
 Param groups (``FusedAdamW([dict(params=..., lr=...), ...])``, at most ``VK_ADAMW_MAX_GROUPS``; ``vk.finetune_groups`` builds the usual
 ones): every tensor takes ``lr``, ``betas``, ``eps`` and ``weight_decay`` from its group, in the same two launches
@@ -24,8 +24,8 @@ ones): every tensor takes ``lr``, ``betas``, ``eps`` and ``weight_decay`` from i
 coefficient on the device for the next ``step()``, which folds it into its gradient factor: **``p.grad`` is not rewritten** (torch
 scales the gradients in place; here they keep their unclipped values), there is no second pass and no host sync.  Which kernel a
 ``step()`` launches: one group, no pending coefficient, every tensor active and no per-tensor counters yet -> ``vk_adamw_step_amp``
-(what ``vk.adamw_for(model, lr, wd)`` has always launched); one group, no pending coefficient and a partial set or per-tensor
-counters -> ``vk_adamw_step_amp_segments``; anything else -> ``vk_adamw_step_groups`` over the active tensors."""
+(what ``vk.adamw_for(model, lr, wd)`` has always launched); anything else -> ``vk_adamw_step_groups`` over the active tensors (with one
+group its group table holds zeros).  Both run the same element function, so the same values give the same bits."""
 from __future__ import annotations
 
 import ctypes as C
@@ -59,7 +59,7 @@ class FusedAdamW(torch.optim.Optimizer):
         self._pending_step = 0          # step count loaded from a state dict before the device buffers exist
         self.grad_inv_scale = 1.0       # extra factor applied to gradients inside the kernel (DP averaging)
         # per-tensor steps (fine-tuning): int32 [tensors] on the device, created from _step_dev by the first step that leaves a tensor
-        # out; from then on every step runs the segmented kernel.  None while every step has covered every tensor.
+        # out; from then on every step runs the per-tensor kernel.  None while every step has covered every tensor.
         self._steps_dev: Optional[torch.Tensor] = None
         self._pending_steps: Optional[List[int]] = None     # per-tensor counts loaded from a state dict
         self._owned: List[Tuple[int, torch.nn.Parameter]] = []   # (tensor index in the model's table, parameter)
@@ -189,26 +189,21 @@ class FusedAdamW(torch.optim.Optimizer):
             fi = fi.reshape(-1)[:1].to(device=p.device, dtype=torch.float32)
         if gs is not None:
             gs = gs.reshape(-1)[:1].to(device=p.device, dtype=torch.float32)
-        if len(self.param_groups) > 1 or clip is not None:
+        if len(self.param_groups) > 1 or clip is not None or len(active) < len(m._param_list) or self._steps_dev is not None:
             self._step_groups(m, active, gs, fi, clip)
-            m.mark_weights_dirty()
-            return None
-        grp = self.param_groups[0]
-        if len(active) < len(m._param_list) or self._steps_dev is not None:
-            self._step_segments(m, active, grp, gs, fi)
-            m.mark_weights_dirty()
-            return None
-        check(lib().vk_adamw_step_amp(p.numel(), p.data_ptr(), g.data_ptr(), self._m.data_ptr(), self._v.data_ptr(),
-                                      float(grp["lr"]), float(grp["betas"][0]), float(grp["betas"][1]), float(grp["eps"]),
-                                      float(grp["weight_decay"]), self._step_dev.data_ptr(), float(self.grad_inv_scale),
-                                      _lib.ptr(gs), _lib.ptr(fi), self._scratch.data_ptr(), 0, 0, _lib.current_stream()),
-              "vk_adamw_step_amp")
+        else:                                                 # one group, every tensor, one counter: the whole buffer
+            grp = self.param_groups[0]
+            check(lib().vk_adamw_step_amp(p.numel(), p.data_ptr(), g.data_ptr(), self._m.data_ptr(), self._v.data_ptr(),
+                                          float(grp["lr"]), float(grp["betas"][0]), float(grp["betas"][1]), float(grp["eps"]),
+                                          float(grp["weight_decay"]), self._step_dev.data_ptr(), float(self.grad_inv_scale),
+                                          _lib.ptr(gs), _lib.ptr(fi), self._scratch.data_ptr(), 0, 0, _lib.current_stream()),
+                  "vk_adamw_step_amp")
         m.mark_weights_dirty()
         return None
 
     def _tables(self, m, active: Tuple[int, ...]):
-        """Segment and block tables of the tensors in `active` (one segment each), shared by the segmented step, the grouped step and
-        the gradient norm."""
+        """Segment and block tables of the tensors in `active` (one segment each), shared by the per-tensor step and the gradient
+        norm."""
         dev = m.flat_params.device
         L = lib()
         if self._seg_key != (active, dev):    # the set of tensors changed: new tables (the only host -> device copies)
@@ -228,26 +223,12 @@ class FusedAdamW(torch.optim.Optimizer):
             self._nblocks = nb
             self._seg_key = (active, dev)
 
-    def _step_segments(self, m, active: Tuple[int, ...], grp, gs, fi):
-        """vk_adamw_step_amp_segments over the tensors in `active`, one segment each, with per-tensor step counters."""
-        p, g = m.flat_params, m.flat_grads
-        L = lib()
-        if self._steps_dev is None:        # first partial step: every tensor has taken the steps of the shared counter so far
-            self._steps_dev = self._step_dev.repeat(len(m._param_list))
-        self._tables(m, active)
-        check(L.vk_adamw_step_amp_segments(len(active), self._seg.data_ptr(), self._nblocks, self._blocks.data_ptr(), p.data_ptr(),
-                                           g.data_ptr(), self._m.data_ptr(), self._v.data_ptr(), float(grp["lr"]),
-                                           float(grp["betas"][0]), float(grp["betas"][1]), float(grp["eps"]), float(grp["weight_decay"]),
-                                           self._steps_dev.data_ptr(), float(self.grad_inv_scale), _lib.ptr(gs), _lib.ptr(fi),
-                                           self._seg_scratch.data_ptr(), _lib.current_stream()),
-              "vk_adamw_step_amp_segments")
-
     def _step_groups(self, m, active: Tuple[int, ...], gs, fi, clip):
         """vk_adamw_step_groups over the tensors in `active`: each with its group's hyper-parameters, the gradient factor times the
         pending clip coefficient (read on the device)."""
         p, g = m.flat_params, m.flat_grads
         dev = p.device
-        if self._steps_dev is None:        # first grouped step: every tensor has taken the steps of the shared counter so far
+        if self._steps_dev is None:        # first per-tensor step: every tensor has taken the steps of the shared counter so far
             self._steps_dev = self._step_dev.repeat(len(m._param_list))
         self._tables(m, active)
         if self._grp_key != (active, dev, self._grouping):     # the set of tensors or the grouping changed

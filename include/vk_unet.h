@@ -23,6 +23,9 @@
  *   vk_adamw_step_amp_segments ................ the same over the tensors that have a gradient (frozen ones are skipped)
  *   vk_adamw_step_groups / vk_grad_norm_segments  param groups ([dict(params=..., lr=...)]) and clip_grad_norm_ (no reference line:
  *                                               the standard fine-tuning recipe around train.py:606)
+ *   vk_avg_update / vk_avg_swap ............... EMA / SWA of the weights and BatchNorm statistics over the flat buffers, and the in-place
+ *                                               exchange that evaluates with them (no reference line: AveragedModel / ModelEmaV2)
+ *   vk_adamw_step_amp_avg ..................... vk_adamw_step_amp with that average updated in the same launch
  *   vk_conv_fwd / vk_conv_wgrad / ... ......... the ATen operators the reference dispatches to
  *                                               (conv2d, batch_norm, relu, max_pool2d, interpolate, cat)
  *   vk_conv_fwd_splitk ........................ the same convolutions at batch 1 (predict_mask / Segmenter.infer)
@@ -987,6 +990,49 @@ int vk_adamw_step_groups(int n_segments, const int64_t* segments, const int32_t*
 #define VK_NORM_INF 1
 int vk_grad_norm_segments(int n_segments, const int64_t* segments, int n_blocks, const int32_t* blocks, const float* grad,
                           int norm_kind, float inv_scale, float max_norm, double* partials, float* out, void* stream);
+
+/* Averaged weights (vk.averaging: torch.optim.swa_utils.AveragedModel / timm's ModelEmaV2 over the flat buffers).
+ * One element rule, with a the average, p the current value and w the fp32 weight of this update:
+ *     w == 1:     a' = p                       (the first SWA sample, or decay 0: a copy, exactly)
+ *     otherwise:  a' = fma(p - a, w, a)        (the difference rounded once, the fused multiply-add once)
+ * The weight is resolved on the device by a one-workgroup prepare step from *count (device int32: updates already taken):
+ *   *found_inf != 0 (the test of vk_adamw_step_amp: 1, -1 and NaN all skip): the average and *count stay as they are; otherwise
+ *   t = *count + 1 is stored and w is formed in double and rounded once:
+ *     VK_AVG_EMA: w = (float)(1.0 - d), d = (double)decay, or with warmup min((double)decay, (1 + t) / (10 + t))   (timm's rule);
+ *     VK_AVG_SWA: w = (float)(1.0 / t).
+ *   scratch: float[2] device scratch owned by the caller (scratch[0] = skip flag, scratch[1] = w).
+ * vk_avg_update: ranges_host[0 .. n_ranges) (HOST array, 1 <= n_ranges <= VK_AVG_MAX_RANGES, copied into the launch; a range with
+ *   n == 0 is skipped), all in ONE grid-stride launch after the prepare step: 16-byte accesses where avg and src of a range share their
+ *   offset from a 16-byte boundary, scalar head and tail (or the whole range) otherwise.  No atomics, no workspace beyond scratch.
+ *   avg and src of a range must not overlap and are 4-byte aligned.  found_inf: optional device fp32.
+ * vk_avg_swap: exchanges avg[i] and src[i] over the same kind of ranges in one launch (src IS written here): each thread reads both
+ *   values, then writes both.
+ * vk_adamw_step_amp_avg = vk_adamw_step_amp followed by vk_avg_update({avg, param, n}, {extra_avg, extra_src, extra_n}) with the same
+ *   found_inf, in two launches instead of four: each element of the parameter buffer runs the AdamW update and then the rule above on
+ *   the value it just wrote; the grid-stride loop then runs on over the extra range (extra_n == 0: none) with the rule alone.  A
+ *   skipped step skips both halves and advances neither counter.  Same element functions, same w: the same bits as the two calls.
+ * Argument errors (null pointers, n_ranges outside 1..4, a misaligned range, decay outside [0, 1) or not a number, an unknown kind) return
+ *   VK_ERR_ARG before anything touches the stream. */
+#define VK_AVG_EMA 0
+#define VK_AVG_SWA 1
+#define VK_AVG_MAX_RANGES 4
+typedef struct {
+  int kind;      /* VK_AVG_EMA or VK_AVG_SWA */
+  float decay;   /* in [0, 1); read by VK_AVG_EMA only */
+  int warmup;    /* nonzero: VK_AVG_EMA's decay at update t is min(decay, (1 + t) / (10 + t)) */
+} vk_avg_rule;
+typedef struct {
+  float* avg;
+  const float* src;
+  size_t n;
+} vk_avg_range;
+int vk_avg_update(int n_ranges, const vk_avg_range* ranges_host, vk_avg_rule rule, int* count, const float* found_inf, float* scratch2,
+                  void* stream);
+int vk_avg_swap(int n_ranges, const vk_avg_range* ranges_host, void* stream);
+int vk_adamw_step_amp_avg(size_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
+                          float beta2, float eps, float weight_decay, int* step_count, float inv_scale, const float* grad_scale,
+                          const float* found_inf, float* scratch4, void* lowp_copy, vk_dtype lowp_dtype, float* avg, int* avg_count,
+                          vk_avg_rule rule, float* avg_scratch2, float* extra_avg, const float* extra_src, size_t extra_n, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Engine level: the whole network as one plan

@@ -10,8 +10,9 @@ Import by string (the directory name carries hyphens)::
     optimizer = vk.adamw_for(model, lr=5e-5, weight_decay=1e-4)
 
 Everything heavy runs in libvkunet.so (hand-written HIP); there is no CPU fallback."""
-from . import _lib, augment, encoders, geometry, instances, losses, lovasz, multiclass, parallel, patches, prepost, seglosses, segmetrics, subpix, sweep, synthetic, tiling  # noqa: F401
+from . import _lib, augment, averaging, encoders, geometry, instances, losses, lovasz, multiclass, parallel, patches, prepost, seglosses, segmetrics, subpix, sweep, synthetic, tiling  # noqa: F401
 from .augment import AugmentSampler, DeviceDataset  # noqa: F401
+from .averaging import SWA, ModelEMA  # noqa: F401
 from .patches import PatchDataset, PatchSampler  # noqa: F401
 from .geometry import (postprocess_minarearect_batch, postprocess_minarearect_multi, postprocess_quadrilateral_batch,  # noqa: F401
                        postprocess_quadrilateral_multi)
@@ -33,4 +34,5 @@ __all__ = ["Unet", "build_model", "DiceLoss", "BCEDiceLoss", "multiclass", "enco
            "postprocess_minarearect_multi", "postprocess_minarearect_batch", "postprocess_quadrilateral_multi", "postprocess_quadrilateral_batch",
            "sweep", "ThresholdSweep", "SweepResult", "threshold_sweep", "sweep_hist", "sweep_curves",
            "instances", "ObjectMetrics", "object_metrics", "Detections", "MatchResult",
-           "subpix", "RefinedDetections"]
+           "subpix", "RefinedDetections",
+           "averaging", "ModelEMA", "SWA"]

@@ -142,6 +142,18 @@ class vk_adamw_group(C.Structure):
     _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float)]
 
 
+VK_AVG_EMA, VK_AVG_SWA = 0, 1
+VK_AVG_MAX_RANGES = 4
+
+
+class vk_avg_rule(C.Structure):
+    _fields_ = [("kind", C.c_int), ("decay", C.c_float), ("warmup", C.c_int)]
+
+
+class vk_avg_range(C.Structure):
+    _fields_ = [("avg", C.c_void_p), ("src", C.c_void_p), ("n", C.c_size_t)]
+
+
 class vk_unet_config(C.Structure):
     _fields_ = [("N", C.c_int), ("size", C.c_int), ("dtype", C.c_int), ("training", C.c_int), ("width", C.c_int)]
 
@@ -250,6 +262,10 @@ SIGNATURES = {
     "vk_adamw_step_amp_segments": (ci, [ci, vp, ci, vp, vp, vp, vp, vp, cf, cf, cf, cf, cf, vp, cf, vp, vp, vp, vp]),
     "vk_adamw_step_groups": (ci, [ci, vp, vp, ci, vp, vp, vp, vp, vp, ci, P(vk_adamw_group), vp, cf, vp, vp, vp, vp, vp]),
     "vk_grad_norm_segments": (ci, [ci, vp, ci, vp, vp, ci, cf, cf, vp, vp, vp]),
+    "vk_avg_update": (ci, [ci, P(vk_avg_range), vk_avg_rule, vp, vp, vp, vp]),
+    "vk_avg_swap": (ci, [ci, P(vk_avg_range), vp]),
+    "vk_adamw_step_amp_avg": (ci, [sz, vp, vp, vp, vp, cf, cf, cf, cf, cf, vp, cf, vp, vp, vp, vp, ci, vp, vp, vk_avg_rule, vp, vp, vp, sz,
+                                   vp]),
     "vk_unet_create": (ci, [P(vk_unet_config), P(vp)]),
     "vk_unet_create_ex": (ci, [P(vk_unet_config), ci, P(vp)]),
     "vk_unet_num_classes": (ci, [vp]),

@@ -6,7 +6,11 @@
 //   vk_amp_check_inf / vk_amp_unscale_check ... GradScaler's inf check / unscale over the one flat gradient buffer
 //   vk_grad_norm_segments ..................... L2 or max norm of the gradient over the listed segments only, and torch's clip
 //                                               coefficient of it, in two launches without atomics
-// The update arithmetic is written once, in adamw_elem; every entry point runs it, so they agree bit for bit by construction.
+//   vk_avg_update / vk_avg_swap ............... EMA / SWA of up to four flat ranges in one grid-stride launch (k_avg_ranges), the weight
+//                                               resolved on the device (avg_prepare); the in-place exchange of average and model
+//   vk_adamw_step_amp_avg ..................... vk_adamw_step_amp with the average updated by the same launch (k_adamw_flat<.., true>)
+// The update arithmetic is written once, in adamw_elem, and the averaging rule once, in avg_elem; every entry point runs them, so they
+// agree bit for bit by construction.
 // Reference operators replaced: AdamW (train.py:449, 606), GradScaler's unscale and inf check (train.py:441-445).
 #include <math.h>
 
@@ -41,6 +45,34 @@ __device__ __forceinline__ float adamw_elem(size_t i, float* __restrict__ p, con
   return pi;
 }
 
+// The averaging rule: a the average, p the current value, w the weight of this update.  w == 1 is a copy, exactly
+// (the first SWA sample, decay 0); otherwise the difference is rounded once and the fused multiply-add once.  Returns a'.
+__device__ __forceinline__ float avg_elem(float a, float p, float w) {
+#pragma clang fp contract(off)
+  if (w == 1.f) return p;
+  const float d = p - a;
+  return __builtin_fmaf(d, w, a);
+}
+
+// The weight of the update that follows `*count` updates, by thread 0 of a prepare kernel: st[0] = skip flag; taken: *count = t =
+// *count + 1 and st[1] = w, formed in double and rounded once (EMA: 1 - decay_t, decay_t = decay or timm's min(decay, (1 + t) / (10 + t));
+// SWA: 1 / t).  Skipped: neither *count nor st[1] is written.
+__device__ __forceinline__ void avg_prepare(vk_avg_rule rule, int* __restrict__ count, bool skip, float* __restrict__ st) {
+  st[0] = skip ? 1.f : 0.f;
+  if (skip) return;
+  const int t = *count + 1;
+  *count = t;
+  double w;
+  if (rule.kind == VK_AVG_SWA) {
+    w = 1.0 / (double)t;
+  } else {
+    double d = (double)rule.decay;
+    if (rule.warmup) d = fmin(d, (1.0 + (double)t) / (10.0 + (double)t));
+    w = 1.0 - d;
+  }
+  st[1] = (float)w;
+}
+
 struct AdamwGroupTable {
   vk_adamw_group g[VK_ADAMW_MAX_GROUPS];      // 8 x 20 bytes, passed by value: an LR scheduler changes lr from the host every epoch
 };
@@ -66,16 +98,16 @@ __device__ __forceinline__ float adamw_grad_factor(float inv_scale, const float*
   return (float)(clip_coef ? f * (double)*clip_coef : f);
 }
 
-// One workgroup: resolves the GradScaler protocol on the device (no host round trip, train.py:443-445).
-//   st[0] = skip flag (*found_inf != 0), st[3] = gradient factor;
+// One workgroup: resolves the GradScaler protocol on the device (no host round trip, train.py:443-445).  The body of both prepare
+// kernels; skip is *found_inf != 0.
+//   st[0] = skip flag, st[3] = gradient factor;
 //   with a segment table: st[4 + 2s], st[5 + 2s] = the bias corrections of segment s from its group and its tensor's counter
 //   steps[seg[s][2]], and st[1] = st[2] = 0; without one (seg null, nseg 1): st[1], st[2] = those of the one counter steps[0];
 //   a counter advances only when the step is taken (torch: optimizer.step() is not called on an overflow).
-__global__ __launch_bounds__(256) void k_adamw_prepare(int nseg, const int64_t* __restrict__ seg, const int32_t* __restrict__ seg_group,
-                                                       int* __restrict__ steps, const float* __restrict__ grad_scale,
-                                                       const float* __restrict__ found_inf, const float* __restrict__ clip_coef,
-                                                       AdamwGroupTable hp, int ngroups, float inv_scale, float* __restrict__ st) {
-  const bool skip = found_inf && *found_inf != 0.f;
+__device__ __forceinline__ void adamw_prepare(int nseg, const int64_t* __restrict__ seg, const int32_t* __restrict__ seg_group,
+                                              int* __restrict__ steps, const float* __restrict__ grad_scale, bool skip,
+                                              const float* __restrict__ clip_coef, const AdamwGroupTable& hp, int ngroups, float inv_scale,
+                                              float* __restrict__ st) {
   if (threadIdx.x == 0) {
     st[0] = skip ? 1.f : 0.f;
     if (seg) st[1] = st[2] = 0.f;
@@ -93,6 +125,28 @@ __global__ __launch_bounds__(256) void k_adamw_prepare(int nseg, const int64_t* 
   }
 }
 
+__global__ __launch_bounds__(256) void k_adamw_prepare(int nseg, const int64_t* __restrict__ seg, const int32_t* __restrict__ seg_group,
+                                                       int* __restrict__ steps, const float* __restrict__ grad_scale,
+                                                       const float* __restrict__ found_inf, const float* __restrict__ clip_coef,
+                                                       AdamwGroupTable hp, int ngroups, float inv_scale, float* __restrict__ st) {
+  adamw_prepare(nseg, seg, seg_group, steps, grad_scale, found_inf && *found_inf != 0.f, clip_coef, hp, ngroups, inv_scale, st);
+}
+
+// The same, and the weight of the average's update under the same skip test (vk_adamw_step_amp_avg: one counter, no segment table).
+__global__ __launch_bounds__(256) void k_adamw_prepare_avg(int* __restrict__ steps, const float* __restrict__ grad_scale,
+                                                           const float* __restrict__ found_inf, AdamwGroupTable hp, float inv_scale,
+                                                           float* __restrict__ st, vk_avg_rule rule, int* __restrict__ avg_count,
+                                                           float* __restrict__ avg_st) {
+  const bool skip = found_inf && *found_inf != 0.f;
+  adamw_prepare(1, nullptr, nullptr, steps, grad_scale, skip, nullptr, hp, 1, inv_scale, st);
+  if (threadIdx.x == 0) avg_prepare(rule, avg_count, skip, avg_st);
+}
+
+// The weight alone (vk_avg_update).
+__global__ void k_avg_prepare(vk_avg_rule rule, int* __restrict__ count, const float* __restrict__ found_inf, float* __restrict__ st) {
+  if (threadIdx.x == 0) avg_prepare(rule, count, found_inf && *found_inf != 0.f, st);
+}
+
 // Where k_adamw_flat takes what depends on the step: from the scratch k_adamw_prepare wrote (st, vk_adamw_step_amp), or, with st null,
 // from the host's values and its int flag (vk_adamw_step, whose ABI has no device scratch).
 struct AdamwStepValues {
@@ -101,10 +155,24 @@ struct AdamwStepValues {
   float step_size, bc2_sqrt, factor;
 };
 
-// The whole buffer: a grid-stride loop over [0, n), optionally emitting the 16-bit working copy.
-template <typename LT>
+// What k_adamw_flat<.., true> takes besides: the average of the parameters, the scratch avg_prepare wrote, and one extra range that gets
+// the averaging rule alone.  Empty without the flag, so that instantiation keeps the code it had.
+template <bool AVG>
+struct AdamwFlatAvg {};
+template <>
+struct AdamwFlatAvg<true> {
+  float* avg;
+  const float* st;
+  float* extra_avg;
+  const float* extra_src;
+  size_t extra_n;
+};
+
+// The whole buffer: a grid-stride loop over [0, n), optionally emitting the 16-bit working copy.  AVG: each element then moves its
+// average toward the value just written, and the loop runs on over the extra range.
+template <typename LT, bool AVG>
 __global__ void k_adamw_flat(size_t n, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                             float lr, float beta1, float beta2, float eps, float wd, AdamwStepValues sv, LT* lowp) {
+                             float lr, float beta1, float beta2, float eps, float wd, AdamwStepValues sv, LT* lowp, AdamwFlatAvg<AVG> av) {
   if (sv.st) {
     if (sv.st[0] != 0.f) return;
     sv.step_size = sv.st[1];
@@ -113,9 +181,69 @@ __global__ void k_adamw_flat(size_t n, float* __restrict__ p, const float* __res
   } else if (sv.found_inf && *sv.found_inf) {
     return;
   }
+  float w = 0.f;
+  if constexpr (AVG) w = av.st[1];
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     const float pi = adamw_elem(i, p, g, m, v, lr, beta1, beta2, eps, wd, sv.step_size, sv.bc2_sqrt, sv.factor);
     if (lowp) st1(lowp + i, pi);
+    if constexpr (AVG) av.avg[i] = avg_elem(av.avg[i], pi, w);
+  }
+  if constexpr (AVG) {
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < av.extra_n; i += (size_t)gridDim.x * blockDim.x)
+      av.extra_avg[i] = avg_elem(av.extra_avg[i], av.extra_src[i], w);
+  }
+}
+
+// Up to VK_AVG_MAX_RANGES flat ranges in one grid-stride launch (vk_avg_update, vk_avg_swap).  Per range: scalar accesses up to the first
+// 16-byte boundary of avg, 16-byte accesses, a scalar tail; a range whose avg and src sit at different offsets from a 16-byte boundary is
+// scalar throughout.  SWAP: avg and src exchange their values (both read, then both written); otherwise avg moves toward src by st[1].
+struct AvgRanges {
+  float* avg[VK_AVG_MAX_RANGES];
+  float* src[VK_AVG_MAX_RANGES];
+  size_t n[VK_AVG_MAX_RANGES];
+  int count;
+};
+
+template <bool SWAP>
+__global__ __launch_bounds__(256) void k_avg_ranges(AvgRanges r, const float* __restrict__ st) {
+  float w = 0.f;
+  if constexpr (!SWAP) {
+    if (st[0] != 0.f) return;
+    w = st[1];
+  }
+  const size_t gid = blockIdx.x * (size_t)blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+  for (int k = 0; k < r.count; ++k) {
+    float* const a = r.avg[k];
+    float* const s = r.src[k];
+    const size_t n = r.n[k];
+    const uint32_t mis = (uint32_t)((uintptr_t)a & 15u);
+    const size_t to_boundary = ((16u - mis) & 15u) >> 2;
+    const size_t head = mis == (uint32_t)((uintptr_t)s & 15u) ? (to_boundary < n ? to_boundary : n) : n;
+    const size_t nvec = (n - head) >> 2;
+    const size_t tail_at = head + 4 * nvec;
+    f32x4_t* const a4 = reinterpret_cast<f32x4_t*>(a + head);
+    f32x4_t* const s4 = reinterpret_cast<f32x4_t*>(s + head);
+    for (size_t i = gid; i < nvec; i += stride) {
+      const f32x4_t x = a4[i], y = s4[i];
+      if constexpr (SWAP) {
+        a4[i] = y;
+        s4[i] = x;
+      } else {
+        a4[i] = f32x4_t{avg_elem(x[0], y[0], w), avg_elem(x[1], y[1], w), avg_elem(x[2], y[2], w), avg_elem(x[3], y[3], w)};
+      }
+    }
+    // the scalar elements: [0, head) and [tail_at, n), one per thread in grid-stride order (a scalar range may be long)
+    const size_t nscalar = head + (n - tail_at);
+    for (size_t j = gid; j < nscalar; j += stride) {
+      const size_t i = j < head ? j : tail_at + (j - head);
+      const float x = a[i], y = s[i];
+      if constexpr (SWAP) {
+        a[i] = y;
+        s[i] = x;
+      } else {
+        a[i] = avg_elem(x, y, w);
+      }
+    }
   }
 }
 
@@ -261,19 +389,58 @@ static AdamwGroupTable group_table(const vk_adamw_group* groups_host, int n_grou
 }
 
 // k_adamw_flat over [0, n) with the 16-bit copy of lowp_dtype (none: a null pointer or VK_F32)
+template <bool AVG>
 static void launch_adamw_flat(hipStream_t st, size_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
-                              const vk_adamw_group& h, const AdamwStepValues& sv, void* lowp_copy, vk_dtype lowp_dtype) {
+                              const vk_adamw_group& h, const AdamwStepValues& sv, void* lowp_copy, vk_dtype lowp_dtype,
+                              const AdamwFlatAvg<AVG>& av) {
   const dim3 grid(grid_for(n)), block(256);
   if (!lowp_copy || lowp_dtype == VK_F32) {
-    hipLaunchKernelGGL(k_adamw_flat<float>, grid, block, 0, st, n, param, grad, exp_avg, exp_avg_sq, h.lr, h.beta1, h.beta2, h.eps,
-                       h.weight_decay, sv, (float*)nullptr);
+    hipLaunchKernelGGL((k_adamw_flat<float, AVG>), grid, block, 0, st, n, param, grad, exp_avg, exp_avg_sq, h.lr, h.beta1, h.beta2, h.eps,
+                       h.weight_decay, sv, (float*)nullptr, av);
   } else if (lowp_dtype == VK_BF16) {
-    hipLaunchKernelGGL(k_adamw_flat<bf16_t>, grid, block, 0, st, n, param, grad, exp_avg, exp_avg_sq, h.lr, h.beta1, h.beta2, h.eps,
-                       h.weight_decay, sv, (bf16_t*)lowp_copy);
+    hipLaunchKernelGGL((k_adamw_flat<bf16_t, AVG>), grid, block, 0, st, n, param, grad, exp_avg, exp_avg_sq, h.lr, h.beta1, h.beta2, h.eps,
+                       h.weight_decay, sv, (bf16_t*)lowp_copy, av);
   } else {
-    hipLaunchKernelGGL(k_adamw_flat<f16_t>, grid, block, 0, st, n, param, grad, exp_avg, exp_avg_sq, h.lr, h.beta1, h.beta2, h.eps,
-                       h.weight_decay, sv, (f16_t*)lowp_copy);
+    hipLaunchKernelGGL((k_adamw_flat<f16_t, AVG>), grid, block, 0, st, n, param, grad, exp_avg, exp_avg_sq, h.lr, h.beta1, h.beta2, h.eps,
+                       h.weight_decay, sv, (f16_t*)lowp_copy, av);
   }
+}
+
+// the rule's own argument checks (every entry point that takes one)
+static bool avg_rule_ok(const char* who, vk_avg_rule rule) {
+  if (rule.kind != VK_AVG_EMA && rule.kind != VK_AVG_SWA) {
+    vkh::set_error("%s: unknown averaging kind %d", who, rule.kind);
+    return false;
+  }
+  if (!(rule.decay >= 0.f && rule.decay < 1.f)) {       // false for a NaN too
+    vkh::set_error("%s: decay must be a number in [0, 1)", who);
+    return false;
+  }
+  return true;
+}
+
+// ranges_host -> the by-value table of k_avg_ranges (empty ranges dropped); false and the error string on a bad one
+static bool avg_ranges(const char* who, int n_ranges, const vk_avg_range* ranges_host, AvgRanges* out, size_t* longest) {
+  if (n_ranges < 1 || n_ranges > VK_AVG_MAX_RANGES || !ranges_host) {
+    vkh::set_error("%s: %d ranges (1..%d are supported, in a non-null array)", who, n_ranges, VK_AVG_MAX_RANGES);
+    return false;
+  }
+  *out = AvgRanges{};
+  *longest = 0;
+  for (int k = 0; k < n_ranges; ++k) {
+    const vk_avg_range& q = ranges_host[k];
+    if (q.n == 0) continue;
+    if (!q.avg || !q.src || (((uintptr_t)q.avg | (uintptr_t)q.src) & 3u)) {
+      vkh::set_error("%s: range %d has a null or misaligned pointer", who, k);
+      return false;
+    }
+    out->avg[out->count] = q.avg;
+    out->src[out->count] = const_cast<float*>(q.src);
+    out->n[out->count] = q.n;
+    ++out->count;
+    if (q.n > *longest) *longest = q.n;
+  }
+  return true;
 }
 
 extern "C" int vk_adamw_step(size_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
@@ -285,7 +452,7 @@ extern "C" int vk_adamw_step(size_t n, float* param, const float* grad, float* e
   const AdamwStepValues sv = {nullptr, found_inf, (float)((double)lr / bc1), (float)sqrt(bc2), inv_scale};
   hipStream_t st = (hipStream_t)stream;
   vkh::ProfScope ps_("adamw", st, 0.0, (double)n * 28.0);
-  launch_adamw_flat(st, n, param, grad, exp_avg, exp_avg_sq, {lr, beta1, beta2, eps, weight_decay}, sv, lowp_copy, lowp_dtype);
+  launch_adamw_flat<false>(st, n, param, grad, exp_avg, exp_avg_sq, {lr, beta1, beta2, eps, weight_decay}, sv, lowp_copy, lowp_dtype, {});
   VK_CHECK_HIP(hipGetLastError());
   return VK_OK;
 }
@@ -299,7 +466,60 @@ extern "C" int vk_adamw_step_amp(size_t n, float* param, const float* grad, floa
   hipLaunchKernelGGL(k_adamw_prepare, dim3(1), dim3(256), 0, st, 1, (const int64_t*)nullptr, (const int32_t*)nullptr, step_count, grad_scale,
                      found_inf, (const float*)nullptr, group_table(&h, 1), 1, inv_scale, scratch4);
   vkh::ProfScope ps_("adamw", st, 0.0, (double)n * 28.0);
-  launch_adamw_flat(st, n, param, grad, exp_avg, exp_avg_sq, h, {scratch4, nullptr, 0.f, 0.f, 0.f}, lowp_copy, lowp_dtype);
+  launch_adamw_flat<false>(st, n, param, grad, exp_avg, exp_avg_sq, h, {scratch4, nullptr, 0.f, 0.f, 0.f}, lowp_copy, lowp_dtype, {});
+  VK_CHECK_HIP(hipGetLastError());
+  return VK_OK;
+}
+
+extern "C" int vk_adamw_step_amp_avg(size_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
+                                     float beta2, float eps, float weight_decay, int* step_count, float inv_scale, const float* grad_scale,
+                                     const float* found_inf, float* scratch4, void* lowp_copy, vk_dtype lowp_dtype, float* avg,
+                                     int* avg_count, vk_avg_rule rule, float* avg_scratch2, float* extra_avg, const float* extra_src,
+                                     size_t extra_n, void* stream) {
+  VK_CHECK_ARG(n > 0 && param && grad && exp_avg && exp_avg_sq && step_count && scratch4, "vk_adamw_step_amp_avg: bad argument");
+  VK_CHECK_ARG(avg && avg_count && avg_scratch2, "vk_adamw_step_amp_avg: null average, counter or scratch");
+  VK_CHECK_ARG(extra_n == 0 || (extra_avg && extra_src), "vk_adamw_step_amp_avg: null extra range");
+  if (!avg_rule_ok("vk_adamw_step_amp_avg", rule)) return VK_ERR_ARG;
+  const vk_adamw_group h = {lr, beta1, beta2, eps, weight_decay};
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_adamw_prepare_avg, dim3(1), dim3(256), 0, st, step_count, grad_scale, found_inf, group_table(&h, 1), inv_scale,
+                     scratch4, rule, avg_count, avg_scratch2);
+  vkh::ProfScope ps_("adamw_avg", st, 0.0, (double)n * 36.0 + (double)extra_n * 12.0);
+  const AdamwFlatAvg<true> av = {avg, avg_scratch2, extra_avg, extra_src, extra_n};
+  launch_adamw_flat<true>(st, n, param, grad, exp_avg, exp_avg_sq, h, {scratch4, nullptr, 0.f, 0.f, 0.f}, lowp_copy, lowp_dtype, av);
+  VK_CHECK_HIP(hipGetLastError());
+  return VK_OK;
+}
+
+// the grid of k_avg_ranges: one thread per 16-byte vector of the longest range, at most 2,048 workgroups
+static dim3 avg_grid(size_t longest) { return dim3(grid_for((longest + 3) / 4, 256, 2048)); }
+
+extern "C" int vk_avg_update(int n_ranges, const vk_avg_range* ranges_host, vk_avg_rule rule, int* count, const float* found_inf,
+                             float* scratch2, void* stream) {
+  AvgRanges r;
+  size_t longest;
+  if (!avg_ranges("vk_avg_update", n_ranges, ranges_host, &r, &longest)) return VK_ERR_ARG;
+  VK_CHECK_ARG(count && scratch2, "vk_avg_update: null counter or scratch");
+  if (!avg_rule_ok("vk_avg_update", rule)) return VK_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_avg_prepare, dim3(1), dim3(64), 0, st, rule, count, found_inf, scratch2);
+  double elems = 0.0;
+  for (int k = 0; k < r.count; ++k) elems += (double)r.n[k];
+  vkh::ProfScope ps_("avg_update", st, 0.0, elems * 12.0);
+  if (r.count) hipLaunchKernelGGL(k_avg_ranges<false>, avg_grid(longest), dim3(256), 0, st, r, (const float*)scratch2);
+  VK_CHECK_HIP(hipGetLastError());
+  return VK_OK;
+}
+
+extern "C" int vk_avg_swap(int n_ranges, const vk_avg_range* ranges_host, void* stream) {
+  AvgRanges r;
+  size_t longest;
+  if (!avg_ranges("vk_avg_swap", n_ranges, ranges_host, &r, &longest)) return VK_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  double elems = 0.0;
+  for (int k = 0; k < r.count; ++k) elems += (double)r.n[k];
+  vkh::ProfScope ps_("avg_swap", st, 0.0, elems * 16.0);
+  if (r.count) hipLaunchKernelGGL(k_avg_ranges<true>, avg_grid(longest), dim3(256), 0, st, r, (const float*)nullptr);
   VK_CHECK_HIP(hipGetLastError());
   return VK_OK;
 }

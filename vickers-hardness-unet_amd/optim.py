@@ -25,7 +25,11 @@ coefficient on the device for the next ``step()``, which folds it into its gradi
 scales the gradients in place; here they keep their unclipped values), there is no second pass and no host sync.  Which kernel a
 ``step()`` launches: one group, no pending coefficient, every tensor active and no per-tensor counters yet -> ``vk_adamw_step_amp``
 (what ``vk.adamw_for(model, lr, wd)`` has always launched); anything else -> ``vk_adamw_step_groups`` over the active tensors (with one
-group its group table holds zeros).  Both run the same element function, so the same values give the same bits."""
+group its group table holds zeros).  Both run the same element function, so the same values give the same bits.
+
+Averaged weights: a ``vk.ModelEMA`` / ``vk.SWA`` attached with ``average.attach(optimizer)`` is updated by every ``step()`` with the
+step's own ``found_inf``: inside the whole-buffer launch (``vk_adamw_step_amp_avg``), or by one ``vk_avg_update`` after
+``vk_adamw_step_groups``.  Without one, ``step()`` launches what it always has."""
 from __future__ import annotations
 
 import ctypes as C
@@ -74,6 +78,7 @@ class FusedAdamW(torch.optim.Optimizer):
         # clip_grad_norm_: float32[1] on the device, consumed (taken or skipped) by the next step(), dropped by zero_grad()
         self._clip_coef: Optional[torch.Tensor] = None
         self._norm_partials = None      # float64 [blocks] scratch of vk_grad_norm_segments
+        self._average = None            # a vk.ModelEMA / vk.SWA that every step() updates (its attach()); None: steps as ever
 
     def add_param_group(self, param_group):
         if len(self.param_groups) >= _lib.VK_ADAMW_MAX_GROUPS:
@@ -173,13 +178,9 @@ class FusedAdamW(torch.optim.Optimizer):
         if not p.is_cuda:
             raise VkError("parameters are on %s: no CPU fallback" % p.device)
         # torch updates the parameters that have a gradient (frozen ones have none after a backward)
-        active = tuple(t for t, q in self._owned if q.grad is not None)
-        if not active:
-            if any(q.requires_grad for _, q in self._owned):
-                raise VkError("optimizer.step() before backward(): gradients are None (zero_grad(set_to_none=True) was the last call)")
-            return None
-        self._ensure_state(p)
-        clip, self._clip_coef = self._clip_coef, None       # consumed by this step, whether found_inf lets it be taken or not
+        avg = self._average
+        if avg is not None:
+            avg._before_step(m)         # raises inside applied(), or when the average no longer matches the model
         # GradScaler support: torch sets these attributes around step() (device tensors; never read on the host here)
         fi = found_inf if found_inf is not None else getattr(self, "found_inf", None)
         gs = grad_scale if grad_scale is not None else getattr(self, "grad_scale", None)
@@ -189,15 +190,35 @@ class FusedAdamW(torch.optim.Optimizer):
             fi = fi.reshape(-1)[:1].to(device=p.device, dtype=torch.float32)
         if gs is not None:
             gs = gs.reshape(-1)[:1].to(device=p.device, dtype=torch.float32)
+        active = tuple(t for t, q in self._owned if q.grad is not None)
+        if not active:
+            if any(q.requires_grad for _, q in self._owned):
+                raise VkError("optimizer.step() before backward(): gradients are None (zero_grad(set_to_none=True) was the last call)")
+            if avg is not None:         # every owned tensor is frozen: the step moves nothing, the average still takes its sample
+                avg._update(fi)
+            return None
+        self._ensure_state(p)
+        clip, self._clip_coef = self._clip_coef, None       # consumed by this step, whether found_inf lets it be taken or not
         if len(self.param_groups) > 1 or clip is not None or len(active) < len(m._param_list) or self._steps_dev is not None:
             self._step_groups(m, active, gs, fi, clip)
+            if avg is not None:         # tensors without a gradient move toward their current value too: the table kernel skips them
+                avg._update(fi)
         else:                                                 # one group, every tensor, one counter: the whole buffer
             grp = self.param_groups[0]
-            check(lib().vk_adamw_step_amp(p.numel(), p.data_ptr(), g.data_ptr(), self._m.data_ptr(), self._v.data_ptr(),
-                                          float(grp["lr"]), float(grp["betas"][0]), float(grp["betas"][1]), float(grp["eps"]),
-                                          float(grp["weight_decay"]), self._step_dev.data_ptr(), float(self.grad_inv_scale),
-                                          _lib.ptr(gs), _lib.ptr(fi), self._scratch.data_ptr(), 0, 0, _lib.current_stream()),
-                  "vk_adamw_step_amp")
+            hp = (float(grp["lr"]), float(grp["betas"][0]), float(grp["betas"][1]), float(grp["eps"]), float(grp["weight_decay"]))
+            if avg is None:
+                check(lib().vk_adamw_step_amp(p.numel(), p.data_ptr(), g.data_ptr(), self._m.data_ptr(), self._v.data_ptr(), *hp,
+                                              self._step_dev.data_ptr(), float(self.grad_inv_scale), _lib.ptr(gs), _lib.ptr(fi),
+                                              self._scratch.data_ptr(), 0, 0, _lib.current_stream()),
+                      "vk_adamw_step_amp")
+            else:                                             # the same step, the average updated by the same launch
+                bufs = m._flat["bufs"]
+                check(lib().vk_adamw_step_amp_avg(p.numel(), p.data_ptr(), g.data_ptr(), self._m.data_ptr(), self._v.data_ptr(), *hp,
+                                                  self._step_dev.data_ptr(), float(self.grad_inv_scale), _lib.ptr(gs), _lib.ptr(fi),
+                                                  self._scratch.data_ptr(), 0, 0, avg._params.data_ptr(), avg._count.data_ptr(),
+                                                  avg._rule(), avg._scratch.data_ptr(), avg._bufs.data_ptr(), bufs.data_ptr(),
+                                                  bufs.numel(), _lib.current_stream()),
+                      "vk_adamw_step_amp_avg")
         m.mark_weights_dirty()
         return None
 

@@ -12,9 +12,8 @@
 // 16-byte channel vectors of a pixel transposed into the same [channel][pixels] LDS image, and the MFMA loop is the forward's.
 // Every 16-bit layer runs v_mfma_f32_16x16x32_{bf16,f16}; fp32 runs v_mfma_f32_16x16x4_f32 (exact fp32 products, fp32 sums).
 #include <algorithm>
-#include <string>
 
-#include "vk_common.h"
+#include "conv_host.h"
 
 namespace vk {
 namespace {
@@ -385,15 +384,9 @@ int conv1x1_fwd_impl(const vk_conv_desc* d, const void* w, void* y, int accumula
   const double flops = 2.0 * p.M * (double)p.Cred * p.Kout;
   const double bytes = ((double)p.M * p.Cred + (double)p.M * p.Kout * (accumulate ? 2.0 : 1.0) + (double)p.Kout * p.Cred) * eb +
                        (d->transposed && sl && !accumulate ? 3.0 * p.M * p.Kout * eb : 0.0);
-  static const std::string tags[2][2] = {{"conv1x1_fwd_f32", "conv1x1_fwd_16b"}, {"conv1x1_dgrad_f32", "conv1x1_dgrad_16b"}};
-  vkh::ProfScope ps(tags[d->transposed ? 1 : 0][eb == 2 ? 1 : 0].c_str(), st, flops, bytes);
-  switch (d->dtype) {
-    case VK_F32: hipLaunchKernelGGL(k_conv1x1_fwd<float>, grid, dim3(256), 0, st, p); break;
-    case VK_BF16: hipLaunchKernelGGL(k_conv1x1_fwd<bf16_t>, grid, dim3(256), 0, st, p); break;
-    case VK_F16: hipLaunchKernelGGL(k_conv1x1_fwd<f16_t>, grid, dim3(256), 0, st, p); break;
-  }
-  VK_CHECK_HIP(hipGetLastError());
-  return VK_OK;
+  static const char* const tags[2][2] = {{"conv1x1_fwd_f32", "conv1x1_fwd_16b"}, {"conv1x1_dgrad_f32", "conv1x1_dgrad_16b"}};
+  const char* const tag = tags[d->transposed ? 1 : 0][eb == 2 ? 1 : 0];
+  return dispatch_dtype(d->dtype, [&](auto e) { return vkh::launch<k_conv1x1_fwd<decltype(e)>>(grid, dim3(256), 0, st, tag, {}, flops, bytes, p); });
 }
 
 int conv1x1_wgrad_impl(const vk_conv_desc* d, const void* dz, float* dw, void* workspace, size_t workspace_bytes, hipStream_t st) {
@@ -426,15 +419,12 @@ int conv1x1_wgrad_impl(const vk_conv_desc* d, const void* dz, float* dw, void* w
   const double flops = 2.0 * p.P * (double)p.K * p.C;
   const double bytes = ((double)p.P * p.K + (double)d->N * d->H * d->W * p.C / (p.s ? 4.0 : 1.0)) * eb +
                        (double)tile_bytes * (splits > 1 ? 2.0 * splits + 2.0 : 2.0);
-  static const std::string tags[2] = {"conv1x1_wgrad_f32", "conv1x1_wgrad_16b"};
-  vkh::ProfScope ps(tags[eb == 2 ? 1 : 0].c_str(), st, flops, bytes);
+  const char* const tag = eb == 2 ? "conv1x1_wgrad_16b" : "conv1x1_wgrad_f32";
   dim3 grid((unsigned)tiles, (unsigned)splits);
-  switch (d->dtype) {
-    case VK_F32: hipLaunchKernelGGL(k_conv1x1_wgrad<float>, grid, dim3(256), 0, st, p); break;
-    case VK_BF16: hipLaunchKernelGGL(k_conv1x1_wgrad<bf16_t>, grid, dim3(256), 0, st, p); break;
-    case VK_F16: hipLaunchKernelGGL(k_conv1x1_wgrad<f16_t>, grid, dim3(256), 0, st, p); break;
+  {
+    const int rc = dispatch_dtype(d->dtype, [&](auto e) { return vkh::launch<k_conv1x1_wgrad<decltype(e)>>(grid, dim3(256), 0, st, tag, {}, flops, bytes, p); });
+    if (rc != VK_OK) return rc;
   }
-  VK_CHECK_HIP(hipGetLastError());
   if (splits > 1) {
     const size_t n = (size_t)p.K * p.C;
     const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 1024);

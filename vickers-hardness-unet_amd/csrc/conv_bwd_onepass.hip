@@ -25,11 +25,11 @@
 #include <string>
 #include <type_traits>
 
-#include "vk_common.h"
+#include "conv_host.h"
 
 namespace vk {
 
-void launch_slab_reduce(size_t n4, int splits, const float* slab, float* dw, hipStream_t st);      // wgrad_halo.hip
+int launch_slab_reduce(size_t n4, int splits, const float* slab, float* dw, hipStream_t st);      // wgrad_halo.hip
 
 struct OnePassParams {
   const void *g, *z, *z1, *w;
@@ -391,13 +391,10 @@ static int launch_onepass(OnePassParams p, float* dw, size_t slab_bytes, hipStre
   }
   RS = (RS + 7) & ~7;
   if (RS < 8) RS = 8;
-  // span of one fp32 partial of the BN-backward sums: launch_stream's strip height (conv_halo.hip), so that the sums are the ones the
-  // streaming data gradient adds up
+  // span of one fp32 partial of the BN-backward sums: the streaming kernel's strip height (stream_strip_rows states the invariant)
   int RSsum = RS;
   if (!e_rs) {
-    const long per_row_block = (long)p.N * ((p.W + 15) / 16);
-    RSsum = 32;
-    while (RSsum * 2 <= 256 && per_row_block * ((p.H + 2 * RSsum - 1) / (2 * RSsum)) >= 4096) RSsum *= 2;
+    RSsum = stream_strip_rows(p.N, p.H, p.W);
     if (RS < RSsum) RS = RSsum;                            // both are 32 << n: RSsum divides RS
   }
   p.RSsum = RSsum;
@@ -405,20 +402,12 @@ static int launch_onepass(OnePassParams p, float* dw, size_t slab_bytes, hipStre
   const long strips = (long)p.N * ((p.H + RS - 1) / RS) * ((p.W + 15) / 16);
   const long nwg = (strips + 3) / 4;
   if ((size_t)nwg * CK * 9 * CK * sizeof(float) > slab_bytes) return VK_ERR_UNSUPPORTED;
-  static bool attr_done = false;
-  if (!attr_done && Cfg::SMEM > 64 * 1024) {
-    VK_CHECK_HIP(hipFuncSetAttribute((const void*)conv_bwd_onepass_kernel<T, CK>, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::SMEM));
-    attr_done = true;
-  }
-  {
-    static const std::string tag = std::string("bwd_onepass_16b_c") + std::to_string(CK);
-    const double px = (double)p.N * p.H * p.W;
-    vkh::ProfScope ps(tag.c_str(), st, 2.0 * 2.0 * px * CK * 9.0 * CK, 4.0 * px * CK * 2.0 + 9.0 * CK * CK * (2.0 + 4.0));
-    hipLaunchKernelGGL((conv_bwd_onepass_kernel<T, CK>), dim3((unsigned)nwg), dim3(256), Cfg::SMEM, st, p);
-  }
-  launch_slab_reduce((size_t)CK * 9 * CK / 4, (int)nwg, p.slab, dw, st);
-  VK_CHECK_HIP(hipGetLastError());
-  return VK_OK;
+  static const std::string tag = std::string("bwd_onepass_16b_c") + std::to_string(CK);
+  const double px = (double)p.N * p.H * p.W;
+  const int rc = vkh::launch<conv_bwd_onepass_kernel<T, CK>>(dim3((unsigned)nwg), dim3(256), Cfg::SMEM, st, tag.c_str(), {}, 2.0 * 2.0 * px * CK * 9.0 * CK,
+                                                             4.0 * px * CK * 2.0 + 9.0 * CK * CK * (2.0 + 4.0), p);
+  if (rc != VK_OK) return rc;
+  return launch_slab_reduce((size_t)CK * 9 * CK / 4, (int)nwg, p.slab, dw, st);
 }
 
 // ---- the upsampled-source form (dec4.conv1: 32 channels at half resolution, nearest x2, -> 16 channels at full resolution).  The three
@@ -792,8 +781,7 @@ static int launch_onepass_up(OnePassParams p, float* dw, size_t slab_bytes, hipS
   if (RS < 8) RS = 8;
   int RSsum = RS;
   if (!e_rs) {
-    RSsum = 32;
-    while (RSsum * 2 <= 256 && per_row_block * ((p.H + 2 * RSsum - 1) / (2 * RSsum)) >= 4096) RSsum *= 2;
+    RSsum = stream_strip_rows(p.N, p.H, p.W);
     if (RS < RSsum) RS = RSsum;                            // both are 32 << n: RSsum divides RS
   }
   p.RSsum = RSsum;
@@ -801,14 +789,11 @@ static int launch_onepass_up(OnePassParams p, float* dw, size_t slab_bytes, hipS
   const long strips = (long)p.N * ((p.H + RS - 1) / RS) * ((p.W + 15) / 16);
   const long nwg = (strips + 3) / 4;
   if ((size_t)nwg * Cfg::K * 9 * Cfg::C * sizeof(float) > slab_bytes) return VK_ERR_UNSUPPORTED;
-  {
-    const double px = (double)p.N * p.H * p.W;
-    vkh::ProfScope ps("bwd_onepass_16b_c32up_k16", st, 2.0 * 2.0 * px * Cfg::K * 9.0 * Cfg::C, 3.0 * px * Cfg::K * 2.0 + 9.0 * Cfg::K * Cfg::C * (2.0 + 4.0));
-    hipLaunchKernelGGL((conv_bwd_onepass_up_kernel<T>), dim3((unsigned)nwg), dim3(256), Cfg::SMEM, st, p);
-  }
-  launch_slab_reduce((size_t)Cfg::K * 9 * Cfg::C / 4, (int)nwg, p.slab, dw, st);
-  VK_CHECK_HIP(hipGetLastError());
-  return VK_OK;
+  const double px = (double)p.N * p.H * p.W;
+  const int rc = vkh::launch<conv_bwd_onepass_up_kernel<T>>(dim3((unsigned)nwg), dim3(256), Cfg::SMEM, st, "bwd_onepass_16b_c32up_k16", {},
+                                                            2.0 * 2.0 * px * Cfg::K * 9.0 * Cfg::C, 3.0 * px * Cfg::K * 2.0 + 9.0 * Cfg::K * Cfg::C * (2.0 + 4.0), p);
+  if (rc != VK_OK) return rc;
+  return launch_slab_reduce((size_t)Cfg::K * 9 * Cfg::C / 4, (int)nwg, p.slab, dw, st);
 }
 
 }  // namespace vk

@@ -19,7 +19,7 @@
 #include <string>
 #include <type_traits>
 
-#include "vk_common.h"
+#include "conv_host.h"
 
 #ifdef VK_STAMP
 #define VK_T(var) { __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_s_waitcnt(0xC07F); __builtin_amdgcn_sched_barrier(0); var = t_; }
@@ -28,14 +28,6 @@
 #endif
 
 namespace vk {
-
-struct HaloSrc {
-  const void* ptr;
-  const float* scale;
-  const float* shift;
-  int C, up, relu;
-  uint32_t bytes;
-};
 
 // -DVK_COLQ_PRE=0: the pipelined K >= 128 kernel's epilogue requests the accumulate / BN-backward operands pass by pass (r03 form)
 #ifndef VK_EPI_BATCH_READS
@@ -54,7 +46,7 @@ struct HaloSrc {
 #define VK_COLQ_PRE 1
 #endif
 struct HaloParams {
-  HaloSrc s0, s1;
+  Src s0, s1;
   const void* w;
   uint32_t w_bytes;
   void* y0;
@@ -453,7 +445,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(const HaloParams p
   auto load_halo = [&](int cc) {
     const int c = cc * CK;
     const bool first = c < p.s0.C;
-    const HaloSrc& sd = first ? p.s0 : p.s1;
+    const Src& sd = first ? p.s0 : p.s1;
     const int cl = (first ? c : c - p.s0.C) + hv * VE;
     aff = sd.scale != nullptr;
     relu = sd.relu != 0;
@@ -728,7 +720,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, MINW) void conv3x3_col_kernel(const
   auto load_halo = [&](int cc) {
     const int c = cc * CK;
     const bool first = c < p.s0.C;
-    const HaloSrc& sd = first ? p.s0 : p.s1;
+    const Src& sd = first ? p.s0 : p.s1;
     const int cl = (first ? c : c - p.s0.C) + hv * VE;
     aff = sd.scale != nullptr;
     relu = sd.relu != 0;
@@ -1156,7 +1148,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, 1) void conv3x3_colq_kernel(const H
   auto load_halo = [&](int cc) {
     const int c = cc * CK;
     const bool first = c < p.s0.C;
-    const HaloSrc& sd = first ? p.s0 : p.s1;
+    const Src& sd = first ? p.s0 : p.s1;
     const int cl = (first ? c : c - p.s0.C) + hv * VE;
     aff = sd.scale != nullptr;
     relu = sd.relu != 0;
@@ -1428,7 +1420,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, 1) void conv3x3_cols_kernel(const H
   auto load_halo = [&](int cc) {
     const int c = cc * CK;
     const bool first = c < p.s0.C;
-    const HaloSrc& sd = first ? p.s0 : p.s1;
+    const Src& sd = first ? p.s0 : p.s1;
     const int cl = (first ? c : c - p.s0.C) + hv * VE;
     aff = sd.scale != nullptr;
     relu = sd.relu != 0;
@@ -1702,7 +1694,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, MINW) void conv3x3_colp_kernel(cons
   auto load_halo = [&](int cc, const int (&hf)[NPV], const int (&hh)[NPV]) {
     const int c = cc * CK;
     const bool first = c < p.s0.C;
-    const HaloSrc& sd = first ? p.s0 : p.s1;
+    const Src& sd = first ? p.s0 : p.s1;
     const int cl = (first ? c : c - p.s0.C) + hv * VE;
     aff = sd.scale != nullptr;
     relu = sd.relu != 0;
@@ -1946,7 +1938,7 @@ int stem_tile_launch(vk_dtype dt, int N, int H, int W, const void* x4, const voi
   if ((size_t)N * H * W * 8 >= (1ull << 31)) return VK_ERR_UNSUPPORTED;
   HaloParams p;
   memset((void*)&p, 0, sizeof(p));
-  p.s0 = HaloSrc{x4, nullptr, nullptr, 4, 0, 0, (uint32_t)((size_t)N * H * W * 8)};
+  p.s0 = plain_src(x4, 4, N, H, W, 2);
   p.w = wp;
   p.w_bytes = 64u * 7u * 32u * 2u;
   p.y0 = y;
@@ -1960,11 +1952,9 @@ int stem_tile_launch(vk_dtype dt, int N, int H, int W, const void* x4, const voi
   constexpr int MAIN = StemTile::W_OFF + StemTile::W_BYTES;
   constexpr int SMEM = MAIN > Cfg::EPI ? MAIN : Cfg::EPI;
   const dim3 grid((unsigned)(N * p.tiles_y * p.tiles_x));
-  vkh::ProfScope ps("stem_tile_16b", st, 2.0 * (double)N * p.H * p.W * 64.0 * 147.0, ((double)N * H * W * 4.0 + (double)N * p.H * p.W * 64.0) * 2.0);
-  if (dt == VK_BF16) hipLaunchKernelGGL(stem7x7_kernel<bf16_t>, grid, dim3(256), SMEM, st, p);
-  else hipLaunchKernelGGL(stem7x7_kernel<f16_t>, grid, dim3(256), SMEM, st, p);
-  VK_CHECK_HIP(hipGetLastError());
-  return VK_OK;
+  const double flops = 2.0 * (double)N * p.H * p.W * 64.0 * 147.0, bytes = ((double)N * H * W * 4.0 + (double)N * p.H * p.W * 64.0) * 2.0;
+  if (dt == VK_BF16) return vkh::launch<stem7x7_kernel<bf16_t>>(grid, dim3(256), SMEM, st, "stem_tile_16b", {}, flops, bytes, p);
+  return vkh::launch<stem7x7_kernel<f16_t>>(grid, dim3(256), SMEM, st, "stem_tile_16b", {}, flops, bytes, p);
 }
 
 // ---- C == 16 (16-bit types): decoder block 4 conv2 and the data gradients whose reduction runs over 16 channels.
@@ -2660,11 +2650,9 @@ int dec4_tail_eval_impl(vk_dtype dt, int N, int H, int W, const vk_src* src, con
   p.src_bytes = (uint32_t)((size_t)N * (H / 2) * (W / 2) * 32 * 2);
   const unsigned nb = (unsigned)((size_t)N * (H / 16) * (W / 16));
   const double px = (double)N * H * W;
-  vkh::ProfScope ps("dec4_tail_eval_16b", st, 2.0 * px * (9.0 * 32 * 16 + 9.0 * 16 * 16 + 144.0), px * (32.0 * 2 / 4 + 4.0));
-  if (dt == VK_BF16) hipLaunchKernelGGL(dec4_tail_eval_kernel<bf16_t>, dim3(nb), dim3(256), TailCfg::SMEM, st, p);
-  else hipLaunchKernelGGL(dec4_tail_eval_kernel<f16_t>, dim3(nb), dim3(256), TailCfg::SMEM, st, p);
-  VK_CHECK_HIP(hipGetLastError());
-  return VK_OK;
+  const double flops = 2.0 * px * (9.0 * 32 * 16 + 9.0 * 16 * 16 + 144.0), bytes = px * (32.0 * 2 / 4 + 4.0);
+  if (dt == VK_BF16) return vkh::launch<dec4_tail_eval_kernel<bf16_t>>(dim3(nb), dim3(256), TailCfg::SMEM, st, "dec4_tail_eval_16b", {}, flops, bytes, p);
+  return vkh::launch<dec4_tail_eval_kernel<f16_t>>(dim3(nb), dim3(256), TailCfg::SMEM, st, "dec4_tail_eval_16b", {}, flops, bytes, p);
 }
 
 // ---- weight repack into the halo layout.  src: [rows][9][red] of T (rows = output channels of the GEMM: K for forward
@@ -2704,30 +2692,20 @@ int halo_pack_impl(vk_dtype dt, int rows, int red, const void* src, void* dst, h
 }
 
 // ------------------------------------------------------------------------------------------------ host
+static vkh::ProfDetail hkc_detail(const HaloParams& p) { return {":H%d_K%d_C%d", {p.H, p.K, p.C}}; }
+
 template <typename T, int TH, int BN, int WGM, int WGN>
 static int launch_halo(HaloParams p, hipStream_t st) {
   using Cfg = HaloCfg<T, TH, BN, WGM, WGN>;
   p.tiles_x = (p.W + 15) / 16;
   p.tiles_y = (p.H + TH - 1) / TH;
   dim3 grid((unsigned)(p.N * p.tiles_y * p.tiles_x), (unsigned)((p.K + BN - 1) / BN), 1);
-  static bool attr_done = false;
-  if (!attr_done && Cfg::SMEM > 64 * 1024) {
-    VK_CHECK_HIP(hipFuncSetAttribute((const void*)conv3x3_halo_kernel<T, TH, BN, WGM, WGN>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::SMEM));
-    attr_done = true;
-  }
-  {
-    static const std::string tag_f = std::string("halo_") + (sizeof(T) == 4 ? "f32" : "16b") + "_t" + std::to_string(TH) + "_bn" + std::to_string(BN);
-    static const std::string tag_d = tag_f + "_dgrad";
-    const double macs = (double)p.N * p.H * p.W * p.K * 9.0 * p.C;
-    const double bytes = ((double)p.N * p.H * p.W * (p.C + p.K) + 9.0 * p.K * p.C) * sizeof(T);
-    const std::string& btag = p.flip ? tag_d : tag_f;
-    const std::string dtag = getenv("VK_PROF_DETAIL") ? btag + ":H" + std::to_string(p.H) + "_K" + std::to_string(p.K) + "_C" + std::to_string(p.C) : btag;
-    vkh::ProfScope ps(dtag.c_str(), st, 2.0 * macs, bytes);
-    hipLaunchKernelGGL((conv3x3_halo_kernel<T, TH, BN, WGM, WGN>), grid, dim3(256), Cfg::SMEM, st, p);
-  }
-  VK_CHECK_HIP(hipGetLastError());
-  return VK_OK;
+  static const std::string tag_f = std::string("halo_") + (sizeof(T) == 4 ? "f32" : "16b") + "_t" + std::to_string(TH) + "_bn" + std::to_string(BN);
+  static const std::string tag_d = tag_f + "_dgrad";
+  const double macs = (double)p.N * p.H * p.W * p.K * 9.0 * p.C;
+  const double bytes = ((double)p.N * p.H * p.W * (p.C + p.K) + 9.0 * p.K * p.C) * sizeof(T);
+  return vkh::launch<conv3x3_halo_kernel<T, TH, BN, WGM, WGN>>(grid, dim3(256), Cfg::SMEM, st, (p.flip ? tag_d : tag_f).c_str(), hkc_detail(p), 2.0 * macs,
+                                                               bytes, p);
 }
 
 // y[e] = T(sum_s slab[s][e]) in slice order (reproducible), four elements per thread
@@ -2749,24 +2727,23 @@ __global__ __launch_bounds__(256) void k_splitk_reduce(size_t n4, int splits, co
 template <int PIPE, typename T, int TH, int BN, int WGM, int WGN, bool ADB, int MINW, int STR>
 struct ColLaunch {
   using Cfg = ColCfg<T, TH, BN, WGM, WGN, ADB, STR>;
-  static const void* kernel() { return (const void*)conv3x3_col_kernel<T, TH, BN, WGM, WGN, ADB, MINW, STR>; }
+  static constexpr auto kernel = conv3x3_col_kernel<T, TH, BN, WGM, WGN, ADB, MINW, STR>;
 };
 template <typename T, int TH, int BN, int WGM, int WGN, bool ADB, int MINW>
 struct ColLaunch<1, T, TH, BN, WGM, WGN, ADB, MINW, 1> {
   using Cfg = ColqCfg<T, TH, BN, WGM, WGN>;
-  static const void* kernel() { return (const void*)conv3x3_colq_kernel<T, TH, BN, WGM, WGN>; }
+  static constexpr auto kernel = conv3x3_colq_kernel<T, TH, BN, WGM, WGN>;
 };
 template <typename T, int TH, int BN, int WGM, int WGN, bool ADB, int MINW>
 struct ColLaunch<2, T, TH, BN, WGM, WGN, ADB, MINW, 1> {
   using Cfg = ColsCfg<T, TH, BN, WGM, WGN>;
-  static const void* kernel() { return (const void*)conv3x3_cols_kernel<T, TH, BN, WGM, WGN>; }
+  static constexpr auto kernel = conv3x3_cols_kernel<T, TH, BN, WGM, WGN>;
 };
 
 template <typename T, int TH, int BN, int WGM, int WGN, bool ADB, int MINW, int PIPE = 0, int STR = 1>
 static int launch_col(HaloParams p, hipStream_t st) {
   using Sel = ColLaunch<PIPE, T, TH, BN, WGM, WGN, ADB, MINW, STR>;
   using Cfg = typename Sel::Cfg;
-  const void* const kernel = Sel::kernel();
   p.tiles_x = (p.W + 15) / 16;
   p.tiles_y = (p.H + TH - 1) / TH;
   dim3 grid((unsigned)(p.N * p.tiles_y * p.tiles_x), (unsigned)((p.K + BN - 1) / BN), 1);
@@ -2797,29 +2774,15 @@ static int launch_col(HaloParams p, hipStream_t st) {
     const bool wst = km ? km[0] == 'w' : (size_t)p.w_bytes >= (3u << 20);
     if (PIPE && wst && 8 % p.kyn == 0 && (grid.x / 8) * (8 / p.kyn) * p.kyn == grid.x) p.kyn = -p.kyn;
   }
-  static bool attr_done = false;
-  if (!attr_done && Cfg::SMEM > 64 * 1024) {
-    VK_CHECK_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::SMEM));
-    attr_done = true;
-  }
-  {
-    static const std::string tag_f = std::string(PIPE == 2 ? "cols_" : PIPE == 1 ? "colq_" : "col_") + (sizeof(T) == 4 ? "f32" : "16b") + "_t" + std::to_string(TH) + "_bn" +
-                                     std::to_string(BN) + "_w" + std::to_string(WGM * WGN) + (STR == 2 ? "_s2" : "");
-    static const std::string tag_d = tag_f + "_dgrad";
-    const double macs = (double)p.N * p.H * p.W * p.K * 9.0 * p.C;
-    const double bytes = ((double)p.N * ((double)p.Hi * p.Wi * p.C + (double)p.H * p.W * p.K) + 9.0 * p.K * p.C) * sizeof(T);
-    const std::string& btag = p.flip ? tag_d : tag_f;
-    const std::string dtag = getenv("VK_PROF_DETAIL") ? btag + ":H" + std::to_string(p.H) + "_K" + std::to_string(p.K) + "_C" + std::to_string(p.C) : btag;
-    vkh::ProfScope ps(dtag.c_str(), st, 2.0 * macs, bytes);
-    void* args[] = {(void*)&p};
-    VK_CHECK_HIP(hipLaunchKernel(kernel, grid, dim3(Cfg::NT), args, Cfg::SMEM, st));
-  }
-  if (ks > 1) {
-    vkh::ProfScope ps("splitk_reduce", st, 0.0, (double)out_elems * (4.0 * ks + sizeof(T)));
-    hipLaunchKernelGGL(k_splitk_reduce<T>, dim3((unsigned)((out_elems / 4 + 255) / 256)), dim3(256), 0, st, out_elems / 4, ks, p.slab, (T*)p.y0);
-  }
-  VK_CHECK_HIP(hipGetLastError());
-  return VK_OK;
+  static const std::string tag_f = std::string(PIPE == 2 ? "cols_" : PIPE == 1 ? "colq_" : "col_") + (sizeof(T) == 4 ? "f32" : "16b") + "_t" + std::to_string(TH) + "_bn" +
+                                   std::to_string(BN) + "_w" + std::to_string(WGM * WGN) + (STR == 2 ? "_s2" : "");
+  static const std::string tag_d = tag_f + "_dgrad";
+  const double macs = (double)p.N * p.H * p.W * p.K * 9.0 * p.C;
+  const double bytes = ((double)p.N * ((double)p.Hi * p.Wi * p.C + (double)p.H * p.W * p.K) + 9.0 * p.K * p.C) * sizeof(T);
+  const int rc = vkh::launch<Sel::kernel>(grid, dim3(Cfg::NT), Cfg::SMEM, st, (p.flip ? tag_d : tag_f).c_str(), hkc_detail(p), 2.0 * macs, bytes, p);
+  if (rc != VK_OK || ks == 1) return rc;
+  return vkh::launch<k_splitk_reduce<T>>(dim3((unsigned)((out_elems / 4 + 255) / 256)), dim3(256), 0, st, "splitk_reduce", {}, 0.0,
+                                         (double)out_elems * (4.0 * ks + sizeof(T)), out_elems / 4, ks, (const float*)p.slab, (T*)p.y0);
 }
 
 // persistent launch of conv3x3_colp_kernel: as many workgroups as stay resident (LDS-limited), at least two tiles each
@@ -2837,25 +2800,13 @@ static int launch_colp(HaloParams p, hipStream_t st) {
   long g = 256L * per_cu;
   if (const char* e = getenv("VK_COL_PERSIST_GRID")) g = atol(e) > 0 ? atol(e) : g;      // tests: few workgroups, many tiles each
   if (g > total) g = total;
-  static bool attr_done = false;
-  if (!attr_done && Cfg::SMEM > 64 * 1024) {
-    VK_CHECK_HIP(hipFuncSetAttribute((const void*)conv3x3_colp_kernel<T, TH, BN, WGM, WGN, MINW>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::SMEM));
-    attr_done = true;
-  }
-  {
-    static const std::string tag_f = std::string("col_") + (sizeof(T) == 4 ? "f32" : "16b") + "_t" + std::to_string(TH) + "_bn" + std::to_string(BN) +
-                                     "_w" + std::to_string(WGM * WGN);
-    static const std::string tag_d = tag_f + "_dgrad";
-    const double macs = (double)p.N * p.H * p.W * p.K * 9.0 * p.C;
-    const double bytes = ((double)p.N * p.H * p.W * (p.C + p.K) + 9.0 * p.K * p.C) * sizeof(T);
-    const std::string& btag = p.flip ? tag_d : tag_f;
-    const std::string dtag = getenv("VK_PROF_DETAIL") ? btag + ":H" + std::to_string(p.H) + "_K" + std::to_string(p.K) + "_C" + std::to_string(p.C) : btag;
-    vkh::ProfScope ps(dtag.c_str(), st, 2.0 * macs, bytes);
-    hipLaunchKernelGGL((conv3x3_colp_kernel<T, TH, BN, WGM, WGN, MINW>), dim3((unsigned)g), dim3(Cfg::NT), Cfg::SMEM, st, p);
-  }
-  VK_CHECK_HIP(hipGetLastError());
-  return VK_OK;
+  static const std::string tag_f = std::string("col_") + (sizeof(T) == 4 ? "f32" : "16b") + "_t" + std::to_string(TH) + "_bn" + std::to_string(BN) +
+                                   "_w" + std::to_string(WGM * WGN);
+  static const std::string tag_d = tag_f + "_dgrad";
+  const double macs = (double)p.N * p.H * p.W * p.K * 9.0 * p.C;
+  const double bytes = ((double)p.N * p.H * p.W * (p.C + p.K) + 9.0 * p.K * p.C) * sizeof(T);
+  return vkh::launch<conv3x3_colp_kernel<T, TH, BN, WGM, WGN, MINW>>(dim3((unsigned)g), dim3(Cfg::NT), Cfg::SMEM, st, (p.flip ? tag_d : tag_f).c_str(),
+                                                                     hkc_detail(p), 2.0 * macs, bytes, p);
 }
 
 // the K < 128 classes: persistent kernel when a workgroup gets several tiles and nothing needs the split-K path
@@ -2939,16 +2890,11 @@ static int launch_c16(HaloParams p, hipStream_t st) {
   p.tiles_x = (p.W + 15) / 16;
   p.tiles_y = (p.H + 15) / 16;
   dim3 grid((unsigned)(p.N * p.tiles_y * p.tiles_x), (unsigned)((p.K + BN - 1) / BN), 1);
-  {
-    static const std::string tag_f = std::string("c16_16b_bn") + std::to_string(BN);
-    static const std::string tag_d = tag_f + "_dgrad";
-    const std::string& btag = p.flip ? tag_d : tag_f;
-    const double bytes = ((double)p.N * p.H * p.W * (16.0 + p.K * (p.pool2 ? 0.25 : 1.0)) + 9.0 * p.K * 16.0) * 2.0;
-    vkh::ProfScope ps(btag.c_str(), st, 2.0 * (double)p.N * p.H * p.W * p.K * 144.0, bytes);
-    hipLaunchKernelGGL((conv3x3_c16_kernel<T, BN>), grid, dim3(256), Cfg::SMEM, st, p);
-  }
-  VK_CHECK_HIP(hipGetLastError());
-  return VK_OK;
+  static const std::string tag_f = std::string("c16_16b_bn") + std::to_string(BN);
+  static const std::string tag_d = tag_f + "_dgrad";
+  const double bytes = ((double)p.N * p.H * p.W * (16.0 + p.K * (p.pool2 ? 0.25 : 1.0)) + 9.0 * p.K * 16.0) * 2.0;
+  return vkh::launch<conv3x3_c16_kernel<T, BN>>(grid, dim3(256), Cfg::SMEM, st, (p.flip ? tag_d : tag_f).c_str(), {}, 2.0 * (double)p.N * p.H * p.W * p.K * 144.0,
+                                                bytes, p);
 }
 
 template <typename T, int BN>
@@ -2957,37 +2903,22 @@ static int launch_s2dg(HaloParams p, hipStream_t st) {
   p.tiles_x = (p.Wi + 15) / 16;
   p.tiles_y = (p.Hi + 7) / 8;
   dim3 grid((unsigned)(p.N * p.tiles_y * p.tiles_x), (unsigned)((p.K + BN - 1) / BN), 1);
-  static bool attr_done = false;
-  if (!attr_done && Cfg::SMEM > 64 * 1024) {
-    VK_CHECK_HIP(hipFuncSetAttribute((const void*)conv3x3_s2dg_kernel<T, 8, BN, 4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::SMEM));
-    attr_done = true;
-  }
-  {
-    static const std::string tag = std::string("s2dg_") + (sizeof(T) == 4 ? "f32" : "16b") + "_bn" + std::to_string(BN);
-    const std::string dtag = getenv("VK_PROF_DETAIL") ? tag + ":H" + std::to_string(p.H) + "_K" + std::to_string(p.K) + "_C" + std::to_string(p.C) : tag;
-    const double bytes = ((double)p.N * ((double)p.Hi * p.Wi * p.C + (double)p.H * p.W * p.K * (p.accumulate ? 2.0 : 1.0)) + 9.0 * p.K * p.C) * sizeof(T);
-    vkh::ProfScope ps(dtag.c_str(), st, 2.0 * (double)p.N * p.Hi * p.Wi * p.K * 9.0 * p.C, bytes);
-    hipLaunchKernelGGL((conv3x3_s2dg_kernel<T, 8, BN, 4, 2>), grid, dim3(Cfg::NT), Cfg::SMEM, st, p);
-  }
-  VK_CHECK_HIP(hipGetLastError());
-  return VK_OK;
+  static const std::string tag = std::string("s2dg_") + (sizeof(T) == 4 ? "f32" : "16b") + "_bn" + std::to_string(BN);
+  const double bytes = ((double)p.N * ((double)p.Hi * p.Wi * p.C + (double)p.H * p.W * p.K * (p.accumulate ? 2.0 : 1.0)) + 9.0 * p.K * p.C) * sizeof(T);
+  return vkh::launch<conv3x3_s2dg_kernel<T, 8, BN, 4, 2>>(grid, dim3(Cfg::NT), Cfg::SMEM, st, tag.c_str(), hkc_detail(p),
+                                                          2.0 * (double)p.N * p.Hi * p.Wi * p.K * 9.0 * p.C, bytes, p);
 }
 
 template <typename T, int CIN, int TC, bool UP, int MODE>
 static int launch_stream(const HaloParams& p, hipStream_t st) {
   using Cfg = StreamCfg<T, CIN, UP>;
   HaloParams q = p;
-  // strip height: as tall as leaves >= 4096 strips (two rounds of the 2048 resident waves) — fewer prologues and statistics atomics
-  // per output row; measured (profiles/r03/stream_strip_height.log): 512^2 maps best at 128 rows (dec4.conv2 data gradient + reduce
-  // 185 -> 153 us), 256^2 maps at 32-64 (128 rows = 1024 strips: 75 -> 101 us).  VK_STREAM_RS overrides (tests / sweeps).
+  // strip height (stream_strip_rows): fewer prologues and statistics atomics per output row; measured
+  // (profiles/r03/stream_strip_height.log): 512^2 maps best at 128 rows (dec4.conv2 data gradient + reduce 185 -> 153 us), 256^2 maps
+  // at 32-64 (128 rows = 1024 strips: 75 -> 101 us).  VK_STREAM_RS overrides (tests / sweeps).
+  static_assert(Cfg::RS == kStreamStripMin, "the kernel's minimal strip is where stream_strip_rows starts");
   const char* e_rs = getenv("VK_STREAM_RS");
-  int RS = Cfg::RS;
-  if (e_rs) {
-    RS = atoi(e_rs);
-  } else {
-    const long per_row_block = (long)p.N * ((p.W + 15) / 16);
-    while (RS * 2 <= 256 && per_row_block * ((p.H + 2 * RS - 1) / (2 * RS)) >= 4096) RS *= 2;
-  }
+  int RS = e_rs ? atoi(e_rs) : stream_strip_rows(p.N, p.H, p.W);
   RS = (RS + 7) & ~7;
   if (RS < 8) RS = 8;
   q.tiles_y = RS;
@@ -2995,14 +2926,11 @@ static int launch_stream(const HaloParams& p, hipStream_t st) {
   dim3 grid((unsigned)((strips + 3) / 4), 1, 1);
   static const std::string tag_f = std::string("stream_16b_c") + std::to_string(CIN) + (UP ? "up" : "") + "_k" + std::to_string(TC * 16);
   static const std::string tag_d = tag_f + "_dgrad";
-  const std::string& tag = p.flip ? tag_d : tag_f;
   const double in_px = (double)p.N * (p.H >> (UP ? 1 : 0)) * (p.W >> (UP ? 1 : 0));
   const double out_px = (double)p.N * p.H * p.W * (p.pool2 ? 0.25 : 1.0);
   const double bytes = (in_px * CIN + out_px * p.K * (p.bnr_z ? 2.0 : 1.0) + 9.0 * p.K * CIN) * 2.0;
-  vkh::ProfScope ps(tag.c_str(), st, 2.0 * (double)p.N * p.H * p.W * p.K * 9.0 * CIN, bytes);
-  hipLaunchKernelGGL((conv3x3_stream_kernel<T, CIN, TC, UP, MODE>), grid, dim3(256), Cfg::SMEM, st, q);
-  VK_CHECK_HIP(hipGetLastError());
-  return VK_OK;
+  return vkh::launch<conv3x3_stream_kernel<T, CIN, TC, UP, MODE>>(grid, dim3(256), Cfg::SMEM, st, (p.flip ? tag_d : tag_f).c_str(), {},
+                                                                  2.0 * (double)p.N * p.H * p.W * p.K * 9.0 * CIN, bytes, q);
 }
 
 // the streaming kernel is instantiated for the launches of decoder blocks 3 / 4 that it is faster on (one source, K in one part, no
@@ -3024,39 +2952,45 @@ static int stream_try(const HaloParams& p, hipStream_t st) {
   return VK_ERR_UNSUPPORTED;
 }
 
-// returns VK_ERR_UNSUPPORTED when the shape is not covered (caller falls back to the tap-by-tap kernel)
-// w: halo pack (vk_halo_pack) when `packed`, plain [K][3][3][C] otherwise — only the C == 16 kernel takes the plain layout
-int conv3x3_halo_try(const vk_conv_desc* d, const void* w, int packed, void* y, void* y1, int split_k1, int accumulate, double* stats,
-                     int pool2, const vk_bnr* bnr, hipStream_t st, void* workspace, size_t workspace_bytes) {
-  // stride 2 (forward only): the K >= 128 openers of layers 2-4 — even input, no upsample / concat / fused gradient epilogues
-  const bool s2 = d->stride == 2 && !d->transposed && d->H == 2 * d->Ho && d->W == 2 * d->Wo && d->K >= 128 && !d->src0.up && !d->src1.ptr &&
-                  !pool2 && !bnr && !accumulate && !split_k1 && !getenv("VK_NO_S2_TILE");
-  // stride-2 data gradient: dz [H][W] -> dx [2H][2W]; plain or accumulating store only
-  const bool s2d = d->stride == 2 && d->transposed && d->Ho == 2 * d->H && d->Wo == 2 * d->W && d->K >= 64 && d->K % 64 == 0 && !d->src0.up &&
-                   !d->src1.ptr && !d->src0.scale && !pool2 && !bnr && !split_k1 && !getenv("VK_NO_S2_TILE");
-  if (d->R != 3 || d->S != 3 || d->pad != 1) return VK_ERR_UNSUPPORTED;
-  if (!s2 && !s2d && (d->stride != 1 || d->H != d->Ho || d->W != d->Wo)) return VK_ERR_UNSUPPORTED;
+// The tile-kernel class of a descriptor (conv_host.h): what conv3x3_halo_try launches and what vk_unet_bind packs weights for.
+HaloClass halo_class(const vk_conv_desc* d) {
+  if (d->R != 3 || d->S != 3 || d->pad != 1) return HaloClass::NONE;
+  const bool s2_tile = d->stride == 2 && !d->src0.up && !d->src1.ptr && !getenv("VK_NO_S2_TILE");
+  // stride 2 (forward only): the K >= 128 openers of layers 2-4 — even input, no upsample / concat
+  const bool s2 = s2_tile && !d->transposed && d->H == 2 * d->Ho && d->W == 2 * d->Wo && d->K >= 128;
+  // stride-2 data gradient: dz [H][W] -> dx [2H][2W], a materialised dz
+  const bool s2d = s2_tile && d->transposed && d->Ho == 2 * d->H && d->Wo == 2 * d->W && d->K >= 64 && d->K % 64 == 0 && !d->src0.scale;
+  if (!s2 && !s2d && (d->stride != 1 || d->H != d->Ho || d->W != d->Wo)) return HaloClass::NONE;
   const int eb = d->dtype == VK_F32 ? 4 : 2;
   const int ck = 64 / eb;
   const int C = d->src0.C + (d->src1.ptr ? d->src1.C : 0);
   const bool c16 = (eb == 2) && C == 16 && !d->src1.ptr && !d->src0.up && !s2 && !s2d;
+  if (!c16 && (d->src0.C % ck || (d->src1.ptr && d->src1.C % ck))) return HaloClass::NONE;
+  if (d->K % 16) return HaloClass::NONE;
+  if (d->src1.ptr && d->src1.up) return HaloClass::NONE;
+  if ((size_t)d->N * d->H * d->W * C * eb >= (1ull << 31) || (size_t)d->N * d->H * d->W >= (1ull << 31)) return HaloClass::NONE;
+  if (s2d && (size_t)d->N * d->Ho * d->Wo * d->K * eb >= (1ull << 32)) return HaloClass::NONE;
+  return c16 ? HaloClass::C16 : s2 ? HaloClass::S2 : s2d ? HaloClass::S2D : HaloClass::S1;
+}
+
+// returns VK_ERR_UNSUPPORTED when the shape is not covered (caller falls back to the tap-by-tap kernel)
+// w: halo pack (vk_halo_pack) when `packed`, plain [K][3][3][C] otherwise — only the C == 16 kernel takes the plain layout
+int conv3x3_halo_try(const vk_conv_desc* d, const void* w, int packed, void* y, void* y1, int split_k1, int accumulate, double* stats,
+                     int pool2, const vk_bnr* bnr, hipStream_t st, void* workspace, size_t workspace_bytes) {
+  const HaloClass cls = halo_class(d);
+  if (cls == HaloClass::NONE) return VK_ERR_UNSUPPORTED;
+  const bool c16 = cls == HaloClass::C16, s2 = cls == HaloClass::S2, s2d = cls == HaloClass::S2D;
+  // what depends on the call: the stride-2 forward has no fused gradient epilogues, its data gradient a plain or accumulating store only
+  if (s2 && (pool2 || bnr || accumulate || split_k1)) return VK_ERR_UNSUPPORTED;
+  if (s2d && (pool2 || bnr || split_k1)) return VK_ERR_UNSUPPORTED;
   if (c16 ? packed : !packed) return VK_ERR_UNSUPPORTED;
-  if (!c16 && (d->src0.C % ck || (d->src1.ptr && d->src1.C % ck))) return VK_ERR_UNSUPPORTED;
-  if (d->K % 16) return VK_ERR_UNSUPPORTED;
   if (pool2 && ((d->H | d->W) & 1)) return VK_ERR_UNSUPPORTED;
-  if (d->src1.ptr && d->src1.up) return VK_ERR_UNSUPPORTED;
-  if ((size_t)d->N * d->H * d->W * C * eb >= (1ull << 31) || (size_t)d->N * d->H * d->W >= (1ull << 31)) return VK_ERR_UNSUPPORTED;
-  if (s2d && (size_t)d->N * d->Ho * d->Wo * d->K * eb >= (1ull << 32)) return VK_ERR_UNSUPPORTED;
+  const int eb = d->dtype == VK_F32 ? 4 : 2;
+  const int ck = 64 / eb;
+  const int C = d->src0.C + (d->src1.ptr ? d->src1.C : 0);
   HaloParams p;
-  auto mk = [&](const vk_src& s) {
-    HaloSrc h;
-    h.ptr = s.ptr; h.scale = s.scale; h.shift = s.shift; h.C = s.C; h.up = s.up; h.relu = s.relu;
-    h.bytes = s.ptr ? (uint32_t)((size_t)d->N * (d->H >> s.up) * (d->W >> s.up) * s.C * eb) : 0u;
-    return h;
-  };
-  p.s0 = mk(d->src0);
-  if (d->src1.ptr) p.s1 = mk(d->src1);
-  else p.s1 = HaloSrc{nullptr, nullptr, nullptr, 0, 0, 0, 0u};
+  p.s0 = make_src(d->src0, d->N, d->H, d->W, eb);
+  p.s1 = make_src1(d, eb);
   p.w = w;
   p.w_bytes = (uint32_t)((size_t)d->K * 9 * C * eb);
   p.y0 = y; p.y1 = y1; p.split = split_k1;
@@ -3099,29 +3033,14 @@ int conv3x3_halo_try(const vk_conv_desc* d, const void* w, int packed, void* y, 
     // 128 output channels per workgroup unless that leaves CUs idle (layer 4: 64 dz tiles x 2 channel tiles)
     const long tiles = (long)d->N * ((d->H + 7) / 8) * ((d->W + 15) / 16);
     const bool wide = d->K % 128 == 0 && tiles * (d->K / 128) >= 256;
-    switch (d->dtype) {
-      case VK_F32: return wide ? launch_s2dg<float, 128>(p, st) : launch_s2dg<float, 64>(p, st);
-      case VK_BF16: return wide ? launch_s2dg<bf16_t, 128>(p, st) : launch_s2dg<bf16_t, 64>(p, st);
-      case VK_F16: return wide ? launch_s2dg<f16_t, 128>(p, st) : launch_s2dg<f16_t, 64>(p, st);
-    }
-    return VK_ERR_ARG;
+    return dispatch_dtype(d->dtype, [&](auto e) { return wide ? launch_s2dg<decltype(e), 128>(p, st) : launch_s2dg<decltype(e), 64>(p, st); });
   }
   if (s2) {
     p.slab = nullptr;                                      // no split-K on this path
     p.slab_bytes = 0;
-    switch (d->dtype) {
-      case VK_F32: return launch_col<float, 8, 128, 2, 4, false, 1, 0, 2>(p, st);
-      case VK_BF16: return launch_col<bf16_t, 8, 128, 2, 4, false, 1, 0, 2>(p, st);
-      case VK_F16: return launch_col<f16_t, 8, 128, 2, 4, false, 1, 0, 2>(p, st);
-    }
-    return VK_ERR_ARG;
+    return dispatch_dtype(d->dtype, [&](auto e) { return launch_col<decltype(e), 8, 128, 2, 4, false, 1, 0, 2>(p, st); });
   }
-  switch (d->dtype) {
-    case VK_F32: return halo_select<float>(p, st);
-    case VK_BF16: return halo_select<bf16_t>(p, st);
-    case VK_F16: return halo_select<f16_t>(p, st);
-  }
-  return VK_ERR_ARG;
+  return dispatch_dtype(d->dtype, [&](auto e) { return halo_select<decltype(e)>(p, st); });
 }
 
 }  // namespace vk

@@ -18,20 +18,12 @@
 
 #include <string>
 
-#include "vk_common.h"
+#include "conv_host.h"
 
 namespace vk {
 
-struct SrcDev {
-  const void* ptr;
-  const float* scale;
-  const float* shift;
-  int C, up, relu;
-  uint32_t bytes;
-};
-
 struct ConvParams {
-  SrcDev s0, s1;
+  Src s0, s1;
   const void* w;
   uint32_t w_bytes;
   void* y0;
@@ -161,7 +153,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvParams p) {
 #pragma unroll
   for (int j = 0; j < VE; ++j) { sc[j] = 1.f; sh[j] = 0.f; }
 
-  auto load_affine = [&](const SrcDev& sd, int cl) {
+  auto load_affine = [&](const Src& sd, int cl) {
     pend_affine = sd.scale != nullptr;
     pend_relu = sd.relu != 0;
     if (pend_affine) {
@@ -178,7 +170,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvParams p) {
   };
 
   // loads one source's A vectors for tap (r, s), local channel cl
-  auto load_a_src = [&](const SrcDev& sd, __amdgpu_buffer_rsrc_t rs, int cl, int r, int s, bool tap_ok) {
+  auto load_a_src = [&](const Src& sd, __amdgpu_buffer_rsrc_t rs, int cl, int r, int s, bool tap_ok) {
     const int up = sd.up;
     const int Hs = p.H >> up, Ws = p.W >> up;
     vmask = 0;
@@ -443,45 +435,21 @@ static int ilog2_exact(int v) {
   return ((1 << l) == v) ? l : -1;
 }
 
-static SrcDev make_src(const vk_src& s, int N, int H, int W, int ebytes) {
-  SrcDev d;
-  d.ptr = s.ptr;
-  d.scale = s.scale;
-  d.shift = s.shift;
-  d.C = s.C;
-  d.up = s.up;
-  d.relu = s.relu;
-  d.bytes = s.ptr ? (uint32_t)((size_t)N * (H >> s.up) * (W >> s.up) * s.C * ebytes) : 0u;
-  return d;
-}
-
 template <typename T, int BM, int BN, int MODE>
 static int launch_cfg(const ConvParams& p, hipStream_t st) {
   using Cfg = IgemmCfg<T, BM, BN>;
   dim3 grid((p.M + BM - 1) / BM, (p.K + BN - 1) / BN, 1);
-  static bool attr_done = false;
-  if (!attr_done && Cfg::SMEM > 64 * 1024) {
-    VK_CHECK_HIP(hipFuncSetAttribute((const void*)conv_igemm_kernel<T, BM, BN, MODE>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::SMEM));
-    attr_done = true;
-  }
-  {
-    static const std::string tag = std::string(MODE == 2 ? "stem_" : "igemm_") + (sizeof(T) == 4 ? "f32" : "16b") + "_bn" + std::to_string(BN) +
-                                   (MODE == 1 ? "_c16" : "");
-    static const std::string tag_t = tag + "_dgrad";
-    // algorithmic work: real conv MACs (the stride-2 transposed gather executes stride^2 x more) and one read of the
-    // input + weights, one write of the output
-    const double macs = (double)p.M * p.K * (MODE == 2 ? 147.0 : (double)p.RSC) / (p.transposed ? (double)(1 << (2 * p.slog)) : 1.0);
-    const double eb = sizeof(T);
-    const double in_px = p.transposed ? (double)p.N * p.H * p.W : (double)p.N * p.H * p.W;
-    const double bytes = (in_px * (MODE == 2 ? 3 : p.C) + (double)p.M * p.K + (double)p.K * (MODE == 2 ? 147.0 : (double)p.RSC)) * eb;
-    const std::string& btag = p.transposed ? tag_t : tag;
-    const std::string dtag = getenv("VK_PROF_DETAIL") ? btag + ":H" + std::to_string(p.H) + "_K" + std::to_string(p.K) + "_C" + std::to_string(p.C) + "_R" + std::to_string(p.R) : btag;
-    vkh::ProfScope ps(dtag.c_str(), st, 2.0 * macs, bytes);
-    hipLaunchKernelGGL((conv_igemm_kernel<T, BM, BN, MODE>), grid, dim3(256), Cfg::SMEM, st, p);
-  }
-  VK_CHECK_HIP(hipGetLastError());
-  return VK_OK;
+  static const std::string tag = std::string(MODE == 2 ? "stem_" : "igemm_") + (sizeof(T) == 4 ? "f32" : "16b") + "_bn" + std::to_string(BN) +
+                                 (MODE == 1 ? "_c16" : "");
+  static const std::string tag_t = tag + "_dgrad";
+  // algorithmic work: real conv MACs (the stride-2 transposed gather executes stride^2 x more) and one read of the
+  // input + weights, one write of the output
+  const double macs = (double)p.M * p.K * (MODE == 2 ? 147.0 : (double)p.RSC) / (p.transposed ? (double)(1 << (2 * p.slog)) : 1.0);
+  const double eb = sizeof(T);
+  const double in_px = (double)p.N * p.H * p.W;
+  const double bytes = (in_px * (MODE == 2 ? 3 : p.C) + (double)p.M * p.K + (double)p.K * (MODE == 2 ? 147.0 : (double)p.RSC)) * eb;
+  return vkh::launch<conv_igemm_kernel<T, BM, BN, MODE>>(grid, dim3(256), Cfg::SMEM, st, (p.transposed ? tag_t : tag).c_str(),
+                                                         {":H%d_K%d_C%d_R%d", {p.H, p.K, p.C, p.R}}, 2.0 * macs, bytes, p);
 }
 
 template <typename T, int MODE>
@@ -503,13 +471,7 @@ static int launch_mode(const ConvParams& p, int mode, hipStream_t st) {
 }
 
 static int dispatch(vk_dtype dt, const ConvParams& p, int mode, hipStream_t st) {
-  switch (dt) {
-    case VK_F32: return launch_mode<float>(p, mode, st);
-    case VK_BF16: return launch_mode<bf16_t>(p, mode, st);
-    case VK_F16: return launch_mode<f16_t>(p, mode, st);
-  }
-  vkh::set_error("bad dtype %d", (int)dt);
-  return VK_ERR_ARG;
+  return dispatch_dtype(dt, [&](auto e) { return launch_mode<decltype(e)>(p, mode, st); }, true);
 }
 
 int conv3x3_halo_try(const vk_conv_desc* d, const void* w, int packed, void* y, void* y1, int split_k1, int accumulate, double* stats,
@@ -558,11 +520,7 @@ int conv_fwd_impl(const vk_conv_desc* d, const void* w, int packed, void* y, voi
   }
   ConvParams p;
   p.s0 = make_src(d->src0, d->N, d->H, d->W, eb);
-  if (d->src1.ptr) {
-    p.s1 = make_src(d->src1, d->N, d->H, d->W, eb);
-  } else {
-    p.s1 = SrcDev{nullptr, nullptr, nullptr, 0, 0, 0, 0u};
-  }
+  p.s1 = make_src1(d, eb);
   const size_t in_bytes = (size_t)d->N * d->H * d->W * C * eb, out_bytes = (size_t)d->N * d->Ho * d->Wo * d->K * eb;
   VK_CHECK_ARG(in_bytes < (1ull << 31) && out_bytes < (1ull << 32), "vk_conv_fwd: tensor too large for 32-bit offsets");
   p.w = w;
@@ -613,8 +571,8 @@ int stem_fwd_impl(vk_dtype dt, int N, int H, int W, const void* x4, const void* 
   }
   const int eb = dt == VK_F32 ? 4 : 2;
   ConvParams p;
-  p.s0 = SrcDev{x4, nullptr, nullptr, 4, 0, 0, (uint32_t)((size_t)N * H * W * 4 * eb)};
-  p.s1 = SrcDev{nullptr, nullptr, nullptr, 0, 0, 0, 0u};
+  p.s0 = plain_src(x4, 4, N, H, W, eb);
+  p.s1 = no_src();
   p.w = wp;
   p.RS = 7;
   p.RSC = 7 * 32;
@@ -668,18 +626,9 @@ extern "C" int vk_halo_pack(vk_dtype dtype, int rows, int red, const void* src, 
 }
 
 extern "C" int vk_conv_uses_halo_pack(const vk_conv_desc* d) {
-  if (!d || d->R != 3 || d->S != 3 || d->pad != 1) return 0;
-  const bool s2 = d->stride == 2 && !d->transposed && d->H == 2 * d->Ho && d->W == 2 * d->Wo && d->K >= 128 && !d->src0.up && !d->src1.ptr &&
-                  !getenv("VK_NO_S2_TILE");                 // the stride-2 forward tile kernel (conv3x3_halo_try)
-  const bool s2d = d->stride == 2 && d->transposed && d->Ho == 2 * d->H && d->Wo == 2 * d->W && d->K >= 64 && d->K % 64 == 0 && !d->src0.up &&
-                   !d->src1.ptr && !d->src0.scale && !getenv("VK_NO_S2_TILE");      // its data gradient (conv3x3_s2dg_kernel)
-  if (s2d && (size_t)d->N * d->Ho * d->Wo * d->K * (d->dtype == VK_F32 ? 4 : 2) >= (1ull << 32)) return 0;
-  if (!s2 && !s2d && (d->stride != 1 || d->H != d->Ho || d->W != d->Wo)) return 0;
-  if (vk::is_c16(d)) return 0;
-  const int ck = d->dtype == VK_F32 ? 16 : 32;
-  if (d->src0.C % ck || (d->src1.ptr && (d->src1.C % ck || d->src1.up)) || d->K % 16) return 0;
-  const size_t C = (size_t)d->src0.C + (d->src1.ptr ? d->src1.C : 0), px = (size_t)d->N * d->H * d->W;
-  if (px * C * (d->dtype == VK_F32 ? 4 : 2) >= (1ull << 31) || px >= (1ull << 31)) return 0;
+  if (!d) return 0;
+  const vk::HaloClass cls = vk::halo_class(d);
+  if (cls == vk::HaloClass::NONE || cls == vk::HaloClass::C16) return 0;      // the C == 16 kernel takes plain weights
   return getenv("VK_NO_HALO") ? 0 : 1;
 }
 

@@ -17,20 +17,12 @@
 
 #include <string>
 
-#include "vk_common.h"
+#include "conv_host.h"
 
 namespace vk {
 
-struct SrcDevW {
-  const void* ptr;
-  const float* scale;
-  const float* shift;
-  int C, up, relu;
-  uint32_t bytes;
-};
-
 struct WgradParams {
-  SrcDevW s0, s1;
+  Src s0, s1;
   const void* dz;
   uint32_t dz_bytes;
   float* dw;
@@ -80,7 +72,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradParams p) {
   if (nch <= 0) return;
 
   const bool first = c0 < p.s0.C;
-  const SrcDevW& sd = first ? p.s0 : p.s1;
+  const Src& sd = first ? p.s0 : p.s1;
   const int cl0 = first ? c0 : c0 - p.s0.C;
   const __amdgpu_buffer_rsrc_t rsv = make_rsrc(sd.ptr, sd.bytes);
   const __amdgpu_buffer_rsrc_t rsz = make_rsrc(p.dz, p.dz_bytes);
@@ -306,7 +298,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradParams p) {
     }
 }
 
-void launch_slab_reduce(size_t n4, int splits, const float* slab, float* dw, hipStream_t st);     // wgrad_halo.hip
+int launch_slab_reduce(size_t n4, int splits, const float* slab, float* dw, hipStream_t st);     // wgrad_halo.hip
 
 // ------------------------------------------------------------------------------------------------ host
 template <typename T, int BMW, int BNW, bool WSPLIT>
@@ -334,26 +326,15 @@ static int launch_w(WgradParams p, void* workspace, size_t workspace_bytes, hipS
   splits = (p.M + p.mps - 1) / p.mps;
   p.slab = use_slab ? (float*)workspace : nullptr;
   dim3 grid(ktiles, p.ctiles * p.RS, splits);
-  static bool attr_done = false;
-  if (!attr_done && Cfg::SMEM > 64 * 1024) {
-    VK_CHECK_HIP(hipFuncSetAttribute((const void*)conv_wgrad_kernel<T, BMW, BNW, WSPLIT>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::SMEM));
-    attr_done = true;
-  }
-  {
-    static const std::string tag_c = std::string("wgrad_") + (sizeof(T) == 4 ? "f32" : "16b") + "_" + std::to_string(BMW) + "x" + std::to_string(BNW);
-    static const std::string tag_s = std::string("wgrad_stem_") + (sizeof(T) == 4 ? "f32" : "16b");
-    const std::string& tag = p.stem ? tag_s : tag_c;
-    const double rsc = p.stem ? 147.0 : (double)p.RS * p.C;
-    const double eb = sizeof(T);
-    const double bytes = ((double)p.N * p.H * p.W * (p.stem ? 3 : p.C) + (double)p.M * p.K) * eb + (double)p.K * rsc * 4.0;
-    const std::string dtag = getenv("VK_PROF_DETAIL") ? tag + ":H" + std::to_string(p.H) + "_K" + std::to_string(p.K) + "_C" + std::to_string(p.C) + "_R" + std::to_string(p.R) + "_s" + std::to_string(splits) : tag;
-    vkh::ProfScope ps(dtag.c_str(), st, 2.0 * (double)p.M * p.K * rsc, bytes);
-    hipLaunchKernelGGL((conv_wgrad_kernel<T, BMW, BNW, WSPLIT>), grid, dim3(256), Cfg::SMEM, st, p);
-  }
-  if (use_slab) launch_slab_reduce(out_elems / 4, splits, p.slab, p.dw, st);
-  VK_CHECK_HIP(hipGetLastError());
-  return VK_OK;
+  static const std::string tag_c = std::string("wgrad_") + (sizeof(T) == 4 ? "f32" : "16b") + "_" + std::to_string(BMW) + "x" + std::to_string(BNW);
+  static const std::string tag_s = std::string("wgrad_stem_") + (sizeof(T) == 4 ? "f32" : "16b");
+  const double rsc = p.stem ? 147.0 : (double)p.RS * p.C;
+  const double eb = sizeof(T);
+  const double bytes = ((double)p.N * p.H * p.W * (p.stem ? 3 : p.C) + (double)p.M * p.K) * eb + (double)p.K * rsc * 4.0;
+  const int rc = vkh::launch<conv_wgrad_kernel<T, BMW, BNW, WSPLIT>>(grid, dim3(256), Cfg::SMEM, st, (p.stem ? tag_s : tag_c).c_str(),
+                                                                     {":H%d_K%d_C%d_R%d_s%d", {p.H, p.K, p.C, p.R, splits}}, 2.0 * (double)p.M * p.K * rsc, bytes, p);
+  if (rc != VK_OK || !use_slab) return rc;
+  return launch_slab_reduce(out_elems / 4, splits, p.slab, p.dw, st);
 }
 
 template <typename T>
@@ -369,20 +350,7 @@ static int launch_w_shape(const WgradParams& p, int cmin, void* ws, size_t wsb, 
 }
 
 static int dispatch_w(vk_dtype dt, const WgradParams& p, int cmin, void* ws, size_t wsb, hipStream_t st) {
-  switch (dt) {
-    case VK_F32: return launch_w_shape<float>(p, cmin, ws, wsb, st);
-    case VK_BF16: return launch_w_shape<bf16_t>(p, cmin, ws, wsb, st);
-    case VK_F16: return launch_w_shape<f16_t>(p, cmin, ws, wsb, st);
-  }
-  vkh::set_error("bad dtype %d", (int)dt);
-  return VK_ERR_ARG;
-}
-
-static SrcDevW make_srcw(const vk_src& s, int N, int H, int W, int eb) {
-  SrcDevW d;
-  d.ptr = s.ptr; d.scale = s.scale; d.shift = s.shift; d.C = s.C; d.up = s.up; d.relu = s.relu;
-  d.bytes = s.ptr ? (uint32_t)((size_t)N * (H >> s.up) * (W >> s.up) * s.C * eb) : 0u;
-  return d;
+  return dispatch_dtype(dt, [&](auto e) { return launch_w_shape<decltype(e)>(p, cmin, ws, wsb, st); }, true);
 }
 
 int wgrad_halo_try(const vk_conv_desc* d, const void* dz, float* dw, void* workspace, size_t workspace_bytes, hipStream_t st);
@@ -401,9 +369,8 @@ int conv_wgrad_impl(const vk_conv_desc* d, const void* dz, float* dw, void* work
   const size_t in_bytes = (size_t)d->N * d->H * d->W * C * eb, dz_bytes = (size_t)d->N * d->Ho * d->Wo * d->K * eb;
   VK_CHECK_ARG(in_bytes < (1ull << 31) && dz_bytes < (1ull << 31), "vk_conv_wgrad: tensor too large for 32-bit offsets");
   WgradParams p;
-  p.s0 = make_srcw(d->src0, d->N, d->H, d->W, eb);
-  if (d->src1.ptr) p.s1 = make_srcw(d->src1, d->N, d->H, d->W, eb);
-  else p.s1 = SrcDevW{nullptr, nullptr, nullptr, 0, 0, 0, 0u};
+  p.s0 = make_src(d->src0, d->N, d->H, d->W, eb);
+  p.s1 = make_src1(d, eb);
   p.dz = dz;
   p.dz_bytes = (uint32_t)dz_bytes;
   p.dw = dw;
@@ -618,23 +585,20 @@ int stem_wgrad_impl(vk_dtype dt, int N, int H, int W, const void* x4, const void
       if ((size_t)nb > cap) nb = (int)cap;
       q.slab = (float*)workspace;
     }
-    static const std::string tag = "wgrad_stem_16b", tag_bn = "wgrad_stem_16b_bn";
-    vkh::ProfScope ps(bn_z ? tag_bn.c_str() : tag.c_str(), st, 2.0 * (double)N * q.Ho * q.Wo * 64.0 * 147.0,
-                      ((double)N * H * W * 4 + (double)N * q.Ho * q.Wo * 64 * (bn_z ? 2 : 1)) * 2.0 + 64.0 * 147 * 4);
-    if (bn_z) {
-      if (dt == VK_BF16) hipLaunchKernelGGL((k_stem_wgrad<bf16_t, true>), dim3((unsigned)nb), dim3(256), 0, st, q);
-      else hipLaunchKernelGGL((k_stem_wgrad<f16_t, true>), dim3((unsigned)nb), dim3(256), 0, st, q);
-    } else {
-      if (dt == VK_BF16) hipLaunchKernelGGL((k_stem_wgrad<bf16_t, false>), dim3((unsigned)nb), dim3(256), 0, st, q);
-      else hipLaunchKernelGGL((k_stem_wgrad<f16_t, false>), dim3((unsigned)nb), dim3(256), 0, st, q);
-    }
-    if (q.slab) launch_slab_reduce(out_elems / 4, nb, q.slab, dw, st);
-    VK_CHECK_HIP(hipGetLastError());
-    return VK_OK;
+    const double flops = 2.0 * (double)N * q.Ho * q.Wo * 64.0 * 147.0;
+    const double bytes = ((double)N * H * W * 4 + (double)N * q.Ho * q.Wo * 64 * (bn_z ? 2 : 1)) * 2.0 + 64.0 * 147 * 4;
+    auto stem = [&](auto e) {
+      using T = decltype(e);
+      if (bn_z) return vkh::launch<k_stem_wgrad<T, true>>(dim3((unsigned)nb), dim3(256), 0, st, "wgrad_stem_16b_bn", {}, flops, bytes, q);
+      return vkh::launch<k_stem_wgrad<T, false>>(dim3((unsigned)nb), dim3(256), 0, st, "wgrad_stem_16b", {}, flops, bytes, q);
+    };
+    const int rc = dt == VK_BF16 ? stem(bf16_t()) : stem(f16_t());
+    if (rc != VK_OK || !q.slab) return rc;
+    return launch_slab_reduce(out_elems / 4, nb, q.slab, dw, st);
   }
   WgradParams p;
-  p.s0 = SrcDevW{x4, nullptr, nullptr, 4, 0, 0, (uint32_t)((size_t)N * H * W * 4 * eb)};
-  p.s1 = SrcDevW{nullptr, nullptr, nullptr, 0, 0, 0, 0u};
+  p.s0 = plain_src(x4, 4, N, H, W, eb);
+  p.s1 = no_src();
   p.dz = dz;
   p.dz_bytes = (uint32_t)((size_t)N * (H / 2) * (W / 2) * 64 * eb);
   p.dw = dw;
@@ -648,12 +612,7 @@ int stem_wgrad_impl(vk_dtype dt, int N, int H, int W, const void* x4, const void
   p.div_hw = vkh::make_fastdiv((uint32_t)(p.Ho * p.Wo));
   p.div_w = vkh::make_fastdiv((uint32_t)p.Wo);
   p.div_s = vkh::make_fastdiv(1);
-  switch (dt) {
-    case VK_F32: return launch_w<float, 64, 32, true>(p, workspace, workspace_bytes, st);
-    case VK_BF16: return launch_w<bf16_t, 64, 32, true>(p, workspace, workspace_bytes, st);
-    case VK_F16: return launch_w<f16_t, 64, 32, true>(p, workspace, workspace_bytes, st);
-  }
-  return VK_ERR_ARG;
+  return dispatch_dtype(dt, [&](auto e) { return launch_w<decltype(e), 64, 32, true>(p, workspace, workspace_bytes, st); });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -768,18 +727,13 @@ static int stem_dgrad_impl(vk_dtype dt, int N, int H, int W, const void* g, cons
   const int cap = dt == VK_F32 ? 512 : 1024;            // persistent: every workgroup builds the weight table once
   const int nb = q.ntiles < cap ? q.ntiles : cap;
   const double eb = dt == VK_F32 ? 4.0 : 2.0;
-  static const std::string tag = "stem_dgrad", tag_bn = "stem_dgrad_bn";
-  vkh::ProfScope ps(coef ? tag_bn.c_str() : tag.c_str(), st, 2.0 * (double)N * q.Ho * q.Wo * 1024.0 * 16.0,
-                    (double)N * q.Ho * q.Wo * 64 * eb * (coef ? 2.0 : 1.0) + (double)N * 3 * H * W * 4.0);
-#define VK_SDG(TT, B) hipLaunchKernelGGL((k_stem_dgrad<TT, B>), dim3((unsigned)nb), dim3(256), 0, st, q)
-  switch (dt) {
-    case VK_F32: if (coef) VK_SDG(float, true); else VK_SDG(float, false); break;
-    case VK_BF16: if (coef) VK_SDG(bf16_t, true); else VK_SDG(bf16_t, false); break;
-    case VK_F16: if (coef) VK_SDG(f16_t, true); else VK_SDG(f16_t, false); break;
-  }
-#undef VK_SDG
-  VK_CHECK_HIP(hipGetLastError());
-  return VK_OK;
+  const double flops = 2.0 * (double)N * q.Ho * q.Wo * 1024.0 * 16.0;
+  const double bytes = (double)N * q.Ho * q.Wo * 64 * eb * (coef ? 2.0 : 1.0) + (double)N * 3 * H * W * 4.0;
+  return dispatch_dtype(dt, [&](auto e) {
+    using T = decltype(e);
+    if (coef) return vkh::launch<k_stem_dgrad<T, true>>(dim3((unsigned)nb), dim3(256), 0, st, "stem_dgrad_bn", {}, flops, bytes, q);
+    return vkh::launch<k_stem_dgrad<T, false>>(dim3((unsigned)nb), dim3(256), 0, st, "stem_dgrad", {}, flops, bytes, q);
+  });
 }
 
 }  // namespace vk

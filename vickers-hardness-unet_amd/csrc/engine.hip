@@ -17,7 +17,7 @@
 #include <string>
 #include <vector>
 
-#include "vk_common.h"
+#include "conv_host.h"
 
 namespace vkh {
 static thread_local char g_err[512] = "";
@@ -63,6 +63,13 @@ ProfScope::ProfScope(const char* tag, hipStream_t stream, double flops, double b
 }
 ProfScope::~ProfScope() {
   if (idx >= 0) (void)hipEventRecord(ev_end, st);
+}
+const char* prof_tag(char* buf, size_t buflen, const char* tag, const ProfDetail& d) {
+  if (!d.fmt || !getenv("VK_PROF_DETAIL")) return tag;
+  const int w = snprintf(buf, buflen, "%s", tag);
+  if (w < 0 || (size_t)w >= buflen) return tag;
+  snprintf(buf + w, buflen - (size_t)w, d.fmt, d.v[0], d.v[1], d.v[2], d.v[3], d.v[4]);
+  return buf;
 }
 }  // namespace vkh
 
@@ -881,6 +888,19 @@ vk_conv_desc conv_desc(const vk_unet* h, const ConvL& c, const vk_src& s0, const
   return d;
 }
 
+// the data gradient of conv c as a convolution: dz (c.g, materialised) -> the layer's input extent, K = its input channels
+vk_conv_desc dgrad_desc(const vk_unet* h, const ConvL& c) {
+  vk_conv_desc d;
+  d.dtype = h->cfg.dtype;
+  d.N = h->cfg.N; d.H = c.Hout; d.W = c.Wout; d.Ho = c.Hin; d.Wo = c.Win;
+  d.K = c.Cin; d.R = c.R; d.S = c.R; d.stride = c.stride; d.pad = c.pad; d.transposed = 1;
+  vk_src s;
+  s.ptr = c.g; s.C = c.K; s.up = 0; s.scale = nullptr; s.shift = nullptr; s.relu = 0;
+  d.src0 = s;
+  d.src1 = null_src();
+  return d;
+}
+
 Act bn_act(const vk_unet* h, const ConvL& c) {   // relu(bn(z)) as a virtual tensor
   const BnL& b = h->bns[c.bn];
   return Act{c.z, c.K, b.scale, b.shift, 1};
@@ -1045,12 +1065,8 @@ extern "C" int vk_unet_bind(vk_unet* h, float* params, float* grads, float* bn_b
     for (size_t i = 0; i < h->convs.size(); ++i) {
       ConvL& c = h->convs[i];
       if (c.wd_off >= 0 && h->cfg.training) {
-        vk_conv_desc d;
-        d.dtype = h->cfg.dtype;
-        d.N = h->cfg.N; d.H = c.Hout; d.W = c.Wout; d.Ho = c.Hin; d.Wo = c.Win;
-        d.K = c.Cin; d.R = c.R; d.S = c.R; d.stride = c.stride; d.pad = c.pad; d.transposed = 1;
-        d.src0 = plain(c.K);
-        d.src1 = null_src();
+        vk_conv_desc d = dgrad_desc(h, c);
+        d.src0.ptr = h->ws;                 // dummy address: the predicate dereferences nothing
         c.halo_dg = vk_conv_uses_halo_pack(&d) != 0;
       }
       HaloPackEntry e;
@@ -1118,12 +1134,7 @@ static int refresh_t(vk_unet* h, hipStream_t st) {
 extern "C" int vk_unet_refresh_weights(vk_unet* h, void* stream) {
   VK_CHECK_ARG(h && h->bound, "vk_unet_refresh_weights: plan not bound");
   hipStream_t st = (hipStream_t)stream;
-  switch (h->cfg.dtype) {
-    case VK_F32: return refresh_t<float>(h, st);
-    case VK_BF16: return refresh_t<bf16_t>(h, st);
-    case VK_F16: return refresh_t<f16_t>(h, st);
-  }
-  return VK_ERR_ARG;
+  return vk::dispatch_dtype(h->cfg.dtype, [&](auto e) { return refresh_t<decltype(e)>(h, st); });
 }
 
 extern "C" int vk_unet_set_side_stream(vk_unet* h, int enable) {
@@ -1348,19 +1359,27 @@ namespace {
 // (k_bn_bwd_coeffs: 8 channels per workgroup, fp64; then the sweep reads 3 C floats) or ONE (vk_bn_bwd_apply_fused: every workgroup of
 // the sweep adds the 32 replicas of all C channels itself — 512 C bytes from L2 per workgroup): the second form takes a launch-bound
 // ~6 us kernel off the critical path where C is small and the tensor large (VK_BN_APPLY_FUSED_MAXC, measured in profiles/r04/).
+// The coefficient launch: (a, b, c) of dz = a*g + b*z + c into b.coef and the gamma / beta gradients, from the sums in b.bsums.  Frozen
+// statistics: (a, 0, 0) is in b.coef since the forward and the sums only give the gamma / beta gradients — no launch when neither trains.
+int bn_bwd_coeffs_launch(vk_unet* h, BnL& b, int C, hipStream_t st) {
+  if (!frozen(h, b))
+    return vk_bn_bwd_coeffs(C, b.bsums, b.count, h->params + b.g_off, b.mean, b.invstd, dgamma_of(h, b), dbeta_of(h, b), b.coef, st);
+  if (!trains(h, b.g_t) && !trains(h, b.b_t)) return VK_OK;
+  return vk_bn_bwd_coeffs_frozen(C, b.bsums, h->params + b.g_off, b.mean, b.invstd, dgamma_of(h, b), dbeta_of(h, b), b.coef, st);
+}
+
+// train-mode layers of up to VK_BN_APPLY_FUSED_MAXC channels: vk_bn_bwd_apply_fused derives the coefficients inside the apply kernel
+bool apply_derives_coeffs(vk_unet* h, BnL& b, int C) {
+  static const int maxc = getenv("VK_BN_APPLY_FUSED_MAXC") ? atoi(getenv("VK_BN_APPLY_FUSED_MAXC")) : VK_BN_APPLY_FUSED_MAXC_DEFAULT;
+  return !frozen(h, b) && C <= maxc;
+}
+
 int bn_bwd_phase2(vk_unet* h, BnL& b, int C, size_t pixels, const void* dy, const void* z, int mask_mode, const void* mask_src, void* dz,
                   void* g_out, int g_acc, hipStream_t st) {
-  static const int maxc = getenv("VK_BN_APPLY_FUSED_MAXC") ? atoi(getenv("VK_BN_APPLY_FUSED_MAXC")) : VK_BN_APPLY_FUSED_MAXC_DEFAULT;
-  if (frozen(h, b)) {
-    // frozen statistics: (a, 0, 0) is in b.coef since the forward; the sums only give gamma / beta gradients
-    if (trains(h, b.g_t) || trains(h, b.b_t))
-      RET_IF(vk_bn_bwd_coeffs_frozen(C, b.bsums, h->params + b.g_off, b.mean, b.invstd, dgamma_of(h, b), dbeta_of(h, b), b.coef, st));
-    return vk_bn_bwd_apply(h->cfg.dtype, pixels, C, dy, z, mask_mode, b.scale, b.shift, mask_src, b.coef, dz, g_out, g_acc, st);
-  }
-  if (C <= maxc)
+  if (apply_derives_coeffs(h, b, C))
     return vk_bn_bwd_apply_fused(h->cfg.dtype, pixels, C, dy, z, mask_mode, b.scale, b.shift, mask_src, b.bsums, b.count, h->params + b.g_off,
                                  b.mean, b.invstd, dgamma_of(h, b), dbeta_of(h, b), dz, g_out, g_acc, st);
-  RET_IF(vk_bn_bwd_coeffs(C, b.bsums, b.count, h->params + b.g_off, b.mean, b.invstd, dgamma_of(h, b), dbeta_of(h, b), b.coef, st));
+  RET_IF(bn_bwd_coeffs_launch(h, b, C, st));
   return vk_bn_bwd_apply(h->cfg.dtype, pixels, C, dy, z, mask_mode, b.scale, b.shift, mask_src, b.coef, dz, g_out, g_acc, st);
 }
 
@@ -1413,18 +1432,6 @@ vk_bnr bnr_of(vk_unet* h, ConvL& target) {     // fused BN+ReLU backward reduce 
   return r;
 }
 
-vk_conv_desc dgrad_desc(vk_unet* h, ConvL& c) {
-  vk_conv_desc d;
-  d.dtype = h->cfg.dtype;
-  d.N = h->cfg.N; d.H = c.Hout; d.W = c.Wout; d.Ho = c.Hin; d.Wo = c.Win;
-  d.K = c.Cin; d.R = c.R; d.S = c.R; d.stride = c.stride; d.pad = c.pad; d.transposed = 1;
-  vk_src s;
-  s.ptr = c.g; s.C = c.K; s.up = 0; s.scale = nullptr; s.shift = nullptr; s.relu = 0;
-  d.src0 = s;
-  d.src1 = null_src();
-  return d;
-}
-
 // dgrad of conv c written to `into.g`, with the BN+ReLU backward reduce of layer `into` fused when the tile kernels
 // cover the shape; *fused tells the caller whether that happened
 int conv_dgrad_into(vk_unet* h, ConvL& c, ConvL& into, bool* fused, hipStream_t st) {
@@ -1451,15 +1458,8 @@ int conv_bwd_onepass(vk_unet* h, ConvL& c, ConvL& into, int up, int* state, hipS
   vk_conv_desc d = conv_desc(h, c, to_src(bn_act(h, into), up), null_src());
   if (d.dtype == VK_F32 || d.R != 3 || d.S != 3 || d.stride != 1 || d.pad != 1) return VK_OK;
   if (up ? (d.src0.C != 32 || d.K != 16 || ((d.H | d.W) & 1)) : (d.src0.C != d.K || (d.K != 16 && d.K != 32))) return VK_OK;
-  static const int maxc = getenv("VK_BN_APPLY_FUSED_MAXC") ? atoi(getenv("VK_BN_APPLY_FUSED_MAXC")) : VK_BN_APPLY_FUSED_MAXC_DEFAULT;
-  if (!frozen(h, b) && c.K <= maxc) return VK_OK;            // that switch derives the coefficients inside the apply kernel
-  // the coefficient launch of bn_bwd_phase2 (frozen statistics: (a, 0, 0) is in b.coef since the forward)
-  if (frozen(h, b)) {
-    if (trains(h, b.g_t) || trains(h, b.b_t))
-      RET_IF(vk_bn_bwd_coeffs_frozen(c.K, b.bsums, h->params + b.g_off, b.mean, b.invstd, dgamma_of(h, b), dbeta_of(h, b), b.coef, st));
-  } else {
-    RET_IF(vk_bn_bwd_coeffs(c.K, b.bsums, b.count, h->params + b.g_off, b.mean, b.invstd, dgamma_of(h, b), dbeta_of(h, b), b.coef, st));
-  }
+  if (apply_derives_coeffs(h, b, c.K)) return VK_OK;         // no b.coef for this kernel to read
+  RET_IF(bn_bwd_coeffs_launch(h, b, c.K, st));
   vk_bnr r = bnr_of(h, into);
   const int rc = vk_conv_bwd_onepass(&d, c.g, c.z, b.coef, dgrad_weights(h, c), into.g, &r, h->grads + c.w_off, h->ws + h->off_wslab,
                                      VK_WGRAD_WORKSPACE_BYTES, st);
@@ -1473,14 +1473,7 @@ int conv_bwd_onepass(vk_unet* h, ConvL& c, ConvL& into, int up, int* state, hipS
 
 // dx = dgrad(dz of conv c) into y (and y1 for the channel split)
 int conv_dgrad(vk_unet* h, ConvL& c, void* y, void* y1, int split, int accumulate, hipStream_t st) {
-  vk_conv_desc d;
-  d.dtype = h->cfg.dtype;
-  d.N = h->cfg.N; d.H = c.Hout; d.W = c.Wout; d.Ho = c.Hin; d.Wo = c.Win;
-  d.K = c.Cin; d.R = c.R; d.S = c.R; d.stride = c.stride; d.pad = c.pad; d.transposed = 1;
-  vk_src s;
-  s.ptr = c.g; s.C = c.K; s.up = 0; s.scale = nullptr; s.shift = nullptr; s.relu = 0;
-  d.src0 = s;
-  d.src1 = null_src();
+  vk_conv_desc d = dgrad_desc(h, c);
   if (on_1x1(c) && !split) return vk_conv1x1_fwd(&d, dgrad_weights(h, c), y, accumulate, nullptr, st);
   if (c.halo_dg) return vk_conv_fwd_packed(&d, dgrad_weights(h, c), y, y1, split, accumulate, nullptr, st);
   return vk_conv_fwd(&d, dgrad_weights(h, c), y, y1, split, accumulate, nullptr, st);
@@ -1574,6 +1567,13 @@ int backward_decoder(vk_unet* h, int i, hipStream_t st) {
   return conv_wgrad(h, c1, to_src(xprev, 1), d.Cskip ? to_src(skip) : null_src(), st);
 }
 
+// the input of encoder block bi (materialised: the pooled stem output or the previous block's output) and its gradient buffer
+std::pair<Act, void*> block_input(vk_unet* h, int bi) {
+  if (bi == 0) return {Act{h->ws + h->off_pool, 64, nullptr, nullptr, 0}, h->ws + h->off_gpool};
+  BlockL& pb = h->blocks[bi - 1];
+  return {Act{pb.out, pb.C, nullptr, nullptr, 0}, pb.gout};
+}
+
 int backward_block(vk_unet* h, int bi, hipStream_t st) {
   BlockL& k = h->blocks[bi];
   ConvL& c1 = h->convs[k.conv1];
@@ -1585,17 +1585,7 @@ int backward_block(vk_unet* h, int bi, hipStream_t st) {
     h->tail_prereduced[(size_t)bi] = 0;
     return VK_OK;
   }
-  // block input (materialised) and its gradient buffer
-  Act xin;
-  void* gin;
-  if (bi == 0) {
-    xin = Act{h->ws + h->off_pool, 64, nullptr, nullptr, 0};
-    gin = h->ws + h->off_gpool;
-  } else {
-    BlockL& pb = h->blocks[bi - 1];
-    xin = Act{pb.out, pb.C, nullptr, nullptr, 0};
-    gin = pb.gout;
-  }
+  const auto [xin, gin] = block_input(h, bi);
   // tail: out = relu(bn2(z2) + shortcut);  g = gout * (out > 0).  r04: when the NEXT block is an identity block, the data gradient of
   // its conv1 — the kernel that completes this block's gout — has already masked it with [out > 0] and added bn2's sums (vk_bnr.mask,
   // see below): no reduce pass here and the apply passes read g as it stands (mask mode 0: one tensor read less each)
@@ -1664,16 +1654,7 @@ int backward_bottleneck(vk_unet* h, int bi, hipStream_t st) {
   const size_t pixels = (size_t)h->cfg.N * k.Hout * k.Wout;
   h->tail_prereduced[(size_t)bi] = 0;
   if (!need_from(h, b3.rank)) return VK_OK;          // frozen from here on (vk_unet_set_trainable)
-  Act xin;
-  void* gin;
-  if (bi == 0) {
-    xin = Act{h->ws + h->off_pool, 64, nullptr, nullptr, 0};
-    gin = h->ws + h->off_gpool;
-  } else {
-    BlockL& pb = h->blocks[bi - 1];
-    xin = Act{pb.out, pb.C, nullptr, nullptr, 0};
-    gin = pb.gout;
-  }
+  const auto [xin, gin] = block_input(h, bi);
   // tail: g = gout * [out > 0] -> dz3 (and dzd, or gin (+)= g through the identity shortcut)
   bool gin_written = k.in_has_grad_first;
   if (bn_sums_needed(h, b3)) RET_IF(vk_bn_bwd_reduce(dt, pixels, k.C, k.gout, c3.z, 2, nullptr, nullptr, k.out, b3.bsums, st));
@@ -1711,14 +1692,8 @@ int backward_bottleneck(vk_unet* h, int bi, hipStream_t st) {
   return trains(h, c1.w_t) ? conv_wgrad(h, c1, to_src(xin), null_src(), st) : VK_OK;
 }
 
-// the stem BatchNorm's coefficients (and gamma / beta gradients) from the sums vk_maxpool_bwd_bn_reduce left; a frozen layer has
-// (a, 0, 0) since the forward and runs the launch only for trainable gamma / beta
-int stem_coeffs(vk_unet* h, BnL& b, hipStream_t st) {
-  if (!frozen(h, b))
-    return vk_bn_bwd_coeffs(64, b.bsums, b.count, h->params + b.g_off, b.mean, b.invstd, dgamma_of(h, b), dbeta_of(h, b), b.coef, st);
-  if (!trains(h, b.g_t) && !trains(h, b.b_t)) return VK_OK;
-  return vk_bn_bwd_coeffs_frozen(64, b.bsums, h->params + b.g_off, b.mean, b.invstd, dgamma_of(h, b), dbeta_of(h, b), b.coef, st);
-}
+// the stem BatchNorm's coefficients (and gamma / beta gradients) from the sums vk_maxpool_bwd_bn_reduce left
+int stem_coeffs(vk_unet* h, BnL& b, hipStream_t st) { return bn_bwd_coeffs_launch(h, b, 64, st); }
 
 int backward_stem(vk_unet* h, hipStream_t st) {
   const int N = h->cfg.N, S = h->cfg.size, SW = h->cfg.width;
@@ -1809,6 +1784,9 @@ int backward_stage(vk_unet* h, const float* dlogits, int stage, hipStream_t st) 
     case 0: {
       if (!need_from(h, 0)) return VK_OK;           // nothing trainable: every stage is a no-op
       VK_CHECK_HIP(hipMemsetAsync(h->ws + h->off_bsums, 0, h->stats_bytes, st));
+      // a backward that failed between two layers may have left a flag set whose sums the memset above just cleared
+      std::fill(h->g_prereduced.begin(), h->g_prereduced.end(), 0);
+      std::fill(h->tail_prereduced.begin(), h->tail_prereduced.end(), 0);
       ConvL& last = h->convs[h->decs[4].conv2];
       const ConvL& head = h->convs[h->head_conv];
       float* const hdw = grad_or_sink(h, head.w_t, h->head_w_off, 2 * h->sink_c);

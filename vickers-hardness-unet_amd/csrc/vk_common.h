@@ -321,6 +321,18 @@ struct ProfScope {
   ProfScope(const char* tag, hipStream_t stream, double flops, double bytes);
   ~ProfScope();
 };
+// Suffix a launch appends to its tag under VK_PROF_DETAIL: `fmt` over up to five integers.  Nothing is formatted or copied unless the
+// switch is set (read per launch).
+struct ProfDetail {
+  const char* fmt = nullptr;
+  int v[5] = {0, 0, 0, 0, 0};
+};
+const char* prof_tag(char* buf, size_t buflen, const char* tag, const ProfDetail& detail);      // tag, or tag + suffix written into buf
+// The one kernel launch of the convolution files (conv_host.h): the dynamic-LDS attribute once per kernel and process, the ProfScope,
+// the launch, the error check.
+template <auto Kernel, typename... Args>
+int launch(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const char* tag, const ProfDetail& detail, double flops, double bytes,
+           const Args&... args);
 }  // namespace vkh
 
 #define VK_CHECK_ARG(cond, ...)                \

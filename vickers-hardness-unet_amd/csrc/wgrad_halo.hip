@@ -17,7 +17,7 @@
 #include <string>
 #include <type_traits>
 
-#include "vk_common.h"
+#include "conv_host.h"
 
 // -DVK_WH_PIPE=1: the fragment reads of the 2x2-wave 16-bit tiles software-pipelined two (step, tap) units ahead (compute_tile_pipe) —
 // built, bit-identical, 174 tests green, and measured 2-3 % SLOWER than the per-step form in same-box A/B runs through VK_LIB
@@ -37,16 +37,8 @@
 
 namespace vk {
 
-struct WhSrc {
-  const void* ptr;
-  const float* scale;
-  const float* shift;
-  int C, up, relu;
-  uint32_t bytes;
-};
-
 struct WhParams {
-  WhSrc s0, s1;
+  Src s0, s1;
   const void* dz;
   uint32_t dz_bytes;
   float* dw;
@@ -109,7 +101,7 @@ __device__ __forceinline__ void wh_segment(const WhParams& p, char* smem, const 
   const int tid = threadIdx.x, lane = tid & 63, wave = (tid >> 6) & 3;
   const int half = __builtin_amdgcn_readfirstlane(tid >> 8);   // tap group (TS); wave-uniform by construction
   const bool first = c0 < p.s0.C;                 // c0: channel in concat space
-  const WhSrc& sd = first ? p.s0 : p.s1;
+  const Src& sd = first ? p.s0 : p.s1;
   const int cl0 = first ? c0 : c0 - p.s0.C;
   const __amdgpu_buffer_rsrc_t rsv = make_rsrc(sd.ptr, sd.bytes);
   const __amdgpu_buffer_rsrc_t rsz = make_rsrc(p.dz, p.dz_bytes);
@@ -887,6 +879,23 @@ __global__ __launch_bounds__(256, (K == 16 ? (UP ? VK_WS_MINWG : 2) : 1)) void w
 // tuning knobs, read per call so that tests can force the kernel onto small problems
 static int wh_max_combo() { const char* e = getenv("VK_WH_MAXCOMBO"); return e ? atoi(e) : 64; }
 static int wh_min_blocks() { const char* e = getenv("VK_WH_MINBLOCKS"); return e ? atoi(e) : 160; }
+// kt x ct output tiles of one layer: deep layers are left to the tap-by-tap kernel (output tile traffic would dominate)
+static bool wh_combo_ok(int kt, int ct) { return kt * ct <= wh_max_combo(); }
+
+// The 64 x 64 tile class of the weight gradient: 16-bit (fp32 double-buffered 64x64 stages would need 197 KB of LDS), K >= 64, every
+// source a multiple of 64 channels (cgran: channel granularity that keeps a c-tile inside one concat source).  TAP_SPLIT is the kernel
+// a batched launch may hold (wgrad_batch_supports); VK_WH_NO_TS (diagnostic) sends the class to the plain 64 x 64 tile.
+enum class Wh64 { NO, PLAIN, TAP_SPLIT };
+static Wh64 wh64_class(int elem_bytes, int K, int cgran) {
+  if (elem_bytes != 2 || K < 64 || cgran % 64) return Wh64::NO;
+  return getenv("VK_WH_NO_TS") ? Wh64::PLAIN : Wh64::TAP_SPLIT;
+}
+
+// the ordered reduce of a slab of partial results; shared with conv_wgrad.hip and conv_bwd_onepass.hip
+int launch_slab_reduce(size_t n4, int splits, const float* slab, float* dw, hipStream_t st) {
+  return vkh::launch<k_wgrad_slab_reduce>(dim3((unsigned)((n4 + 15) / 16)), dim3(256), 0, st, "wgrad_slab_reduce", {}, 0.0, (double)(splits + 2) * n4 * 16.0,
+                                          n4, splits, slab, dw);
+}
 
 template <typename T, int KT, int CT, bool WS, bool TS = false, int STR = 1>
 static int launch_wh(WhParams p, size_t slab_bytes, hipStream_t st) {
@@ -895,7 +904,7 @@ static int launch_wh(WhParams p, size_t slab_bytes, hipStream_t st) {
   p.tiles_y = (p.H + 7) / 8;
   p.ntiles = p.N * p.tiles_y * p.tiles_x;
   const int kt = (p.K + KT - 1) / KT, ct = p.C / CT;
-  if (kt * ct > wh_max_combo()) return VK_ERR_UNSUPPORTED;      // deep layers: output tile traffic would dominate
+  if (!wh_combo_ok(kt, ct)) return VK_ERR_UNSUPPORTED;
   // every workgroup ends with KT*CT*9 fp32 atomics: give it at least ~6 pixel tiles of work
   const char* e_blk = getenv("VK_WH_BLOCKS");
   // non-WS: LDS allows exactly one workgroup per CU; with compute units reserved for a concurrent collective (vk_set_reserved_cus)
@@ -910,32 +919,14 @@ static int launch_wh(WhParams p, size_t slab_bytes, hipStream_t st) {
   const size_t slab_need = (size_t)splits * p.K * 9 * p.C * sizeof(float);
   if (!p.slab || slab_need > slab_bytes || getenv("VK_WH_NO_SLAB")) p.slab = nullptr;
   dim3 grid(kt, ct, splits);
-  static bool attr_done = false;
-  if (!attr_done && Cfg::SMEM > 64 * 1024) {
-    VK_CHECK_HIP(hipFuncSetAttribute((const void*)wgrad_halo_kernel<T, KT, CT, WS, TS, STR>, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::SMEM));
-    attr_done = true;
-  }
-  {
-    static const std::string tag = std::string("wgrad_halo_") + (sizeof(T) == 4 ? "f32" : "16b") + "_" + std::to_string(KT) + "x" + std::to_string(CT) + (TS ? "ts" : "") +
-                                   (STR == 2 ? "_s2" : "");
-    const double bytes = ((double)p.N * p.Hi * p.Wi * p.C + (double)p.N * p.H * p.W * p.K) * sizeof(T) + 9.0 * p.K * p.C * 4.0;
-    const std::string dtag = getenv("VK_PROF_DETAIL") ? tag + ":H" + std::to_string(p.H) + "_K" + std::to_string(p.K) + "_C" + std::to_string(p.C) + "_s" + std::to_string(splits) : tag;
-    vkh::ProfScope ps(dtag.c_str(), st, 2.0 * (double)p.N * p.H * p.W * p.K * 9.0 * p.C, bytes);
-    hipLaunchKernelGGL((wgrad_halo_kernel<T, KT, CT, WS, TS, STR>), grid, dim3(Cfg::NT), Cfg::SMEM, st, p);
-  }
-  if (p.slab) {
-    const size_t n4 = (size_t)p.K * 9 * p.C / 4;
-    vkh::ProfScope ps("wgrad_slab_reduce", st, 0.0, (double)(splits + 2) * n4 * 16.0);
-    hipLaunchKernelGGL(k_wgrad_slab_reduce, dim3((unsigned)((n4 + 15) / 16)), dim3(256), 0, st, n4, splits, p.slab, p.dw);
-  }
-  VK_CHECK_HIP(hipGetLastError());
-  return VK_OK;
-}
-
-// shared with conv_wgrad.hip (tap-by-tap and stem kernels in reproducible mode)
-void launch_slab_reduce(size_t n4, int splits, const float* slab, float* dw, hipStream_t st) {
-  vkh::ProfScope ps("wgrad_slab_reduce", st, 0.0, (double)(splits + 2) * n4 * 16.0);
-  hipLaunchKernelGGL(k_wgrad_slab_reduce, dim3((unsigned)((n4 + 15) / 16)), dim3(256), 0, st, n4, splits, slab, dw);
+  static const std::string tag = std::string("wgrad_halo_") + (sizeof(T) == 4 ? "f32" : "16b") + "_" + std::to_string(KT) + "x" + std::to_string(CT) + (TS ? "ts" : "") +
+                                 (STR == 2 ? "_s2" : "");
+  const double bytes = ((double)p.N * p.Hi * p.Wi * p.C + (double)p.N * p.H * p.W * p.K) * sizeof(T) + 9.0 * p.K * p.C * 4.0;
+  const int rc = vkh::launch<wgrad_halo_kernel<T, KT, CT, WS, TS, STR>>(grid, dim3(Cfg::NT), Cfg::SMEM, st, tag.c_str(),
+                                                                        {":H%d_K%d_C%d_s%d", {p.H, p.K, p.C, splits}},
+                                                                        2.0 * (double)p.N * p.H * p.W * p.K * 9.0 * p.C, bytes, p);
+  if (rc != VK_OK || !p.slab) return rc;
+  return launch_slab_reduce((size_t)p.K * 9 * p.C / 4, splits, p.slab, p.dw, st);
 }
 
 // dw[(kbase + k)][tap][c_dst + c] += sum over the nwg workgroup tiles [KW][9][32] of one (chunk, slice), in workgroup order (same
@@ -990,26 +981,15 @@ static int launch_ws(WhParams p, int c_dst0, char* slab, size_t slab_bytes, size
   const long nwg = (strips + 3) / 4;
   *used = (size_t)nwg * gy * KW * 9 * 32 * sizeof(float);
   if (*used > slab_bytes) return VK_ERR_UNSUPPORTED;
-  static bool attr_done = false;
-  if (!attr_done && Cfg::SMEM > 64 * 1024) {
-    VK_CHECK_HIP(hipFuncSetAttribute((const void*)wgrad_stream_kernel<T, KW, UP>, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::SMEM));
-    attr_done = true;
-  }
   p.slab = (float*)slab;
   WsArgs wa{RS, c_dst0, nks};
-  {
-    static const std::string tag = std::string("wgrad_stream_16b_c32") + (UP ? "up" : "") + "_k" + std::to_string(KW);
-    const double bytes = ((double)p.N * (p.H >> (UP ? 1 : 0)) * (p.W >> (UP ? 1 : 0)) * p.s0.C + (double)p.N * p.H * p.W * p.K) * 2.0 + 9.0 * p.K * p.s0.C * 4.0;
-    vkh::ProfScope ps(tag.c_str(), st, 2.0 * (double)p.N * p.H * p.W * p.K * 9.0 * p.s0.C, bytes);
-    hipLaunchKernelGGL((wgrad_stream_kernel<T, KW, UP>), dim3((unsigned)nwg, (unsigned)gy), dim3(256), Cfg::SMEM, st, p, wa);
-  }
-  {
-    vkh::ProfScope ps("wgrad_slab_reduce", st, 0.0, (double)*used + 2.0 * p.K * 9.0 * p.s0.C * 4.0);
-    hipLaunchKernelGGL(k_ws_slab_reduce, dim3((unsigned)((KW * 9 * 8 + 15) / 16), (unsigned)gy), dim3(256), 0, st, KW, p.C, c_dst0, nks, (int)nwg,
-                       (const float*)slab, p.dw);
-  }
-  VK_CHECK_HIP(hipGetLastError());
-  return VK_OK;
+  static const std::string tag = std::string("wgrad_stream_16b_c32") + (UP ? "up" : "") + "_k" + std::to_string(KW);
+  const double bytes = ((double)p.N * (p.H >> (UP ? 1 : 0)) * (p.W >> (UP ? 1 : 0)) * p.s0.C + (double)p.N * p.H * p.W * p.K) * 2.0 + 9.0 * p.K * p.s0.C * 4.0;
+  const int rc = vkh::launch<wgrad_stream_kernel<T, KW, UP>>(dim3((unsigned)nwg, (unsigned)gy), dim3(256), Cfg::SMEM, st, tag.c_str(), {},
+                                                             2.0 * (double)p.N * p.H * p.W * p.K * 9.0 * p.s0.C, bytes, p, wa);
+  if (rc != VK_OK) return rc;
+  return vkh::launch<k_ws_slab_reduce>(dim3((unsigned)((KW * 9 * 8 + 15) / 16), (unsigned)gy), dim3(256), 0, st, "wgrad_slab_reduce", {}, 0.0,
+                                       (double)*used + 2.0 * p.K * 9.0 * p.s0.C * 4.0, KW, p.C, c_dst0, nks, (int)nwg, (const float*)slab, p.dw);
 }
 
 // Routed here: ONE source of exactly 32 channels (decoder block 3 conv2, block 4 conv1).  The kernel's work units also cover several
@@ -1039,11 +1019,10 @@ static int wh_select(const WhParams& p, int cgran, size_t slab_bytes, hipStream_
     if (rc != VK_ERR_UNSUPPORTED) return rc;
   }
   // cgran: channel granularity that keeps a c-tile inside one concat source
-  if constexpr (sizeof(T) == 2) {      // fp32 double-buffered 64x64 stages would need 197 KB of LDS
-    if (p.K >= 64 && cgran % 64 == 0) {
-      if (getenv("VK_WH_NO_TS")) return launch_wh<T, 64, 64, false>(p, slab_bytes, st);
-      return launch_wh<T, 64, 64, false, true>(p, slab_bytes, st);
-    }
+  if constexpr (sizeof(T) == 2) {
+    const Wh64 c64 = wh64_class(sizeof(T), p.K, cgran);
+    if (c64 == Wh64::PLAIN) return launch_wh<T, 64, 64, false>(p, slab_bytes, st);
+    if (c64 == Wh64::TAP_SPLIT) return launch_wh<T, 64, 64, false, true>(p, slab_bytes, st);
   }
   if constexpr (sizeof(T) == 2) {
     if (p.K >= 32 && cgran % 64 == 0) return launch_wh<T, 32, 64, false, true>(p, slab_bytes, st);   // decoder block 3 conv1
@@ -1064,15 +1043,8 @@ static int make_wh_params(const vk_conv_desc* d, const void* dz, float* dw, WhPa
   int cgran = 64;
   while (cgran > 16 && (d->src0.C % cgran || (d->src1.ptr && d->src1.C % cgran))) cgran >>= 1;
   WhParams p;
-  auto mk = [&](const vk_src& s) {
-    WhSrc h;
-    h.ptr = s.ptr; h.scale = s.scale; h.shift = s.shift; h.C = s.C; h.up = s.up; h.relu = s.relu;
-    h.bytes = s.ptr ? (uint32_t)((size_t)d->N * (d->H >> s.up) * (d->W >> s.up) * s.C * eb) : 0u;
-    return h;
-  };
-  p.s0 = mk(d->src0);
-  if (d->src1.ptr) p.s1 = mk(d->src1);
-  else p.s1 = WhSrc{nullptr, nullptr, nullptr, 0, 0, 0, 0u};
+  p.s0 = make_src(d->src0, d->N, d->H, d->W, eb);
+  p.s1 = make_src1(d, eb);
   p.dz = dz;
   p.dz_bytes = (uint32_t)((size_t)d->N * d->Ho * d->Wo * d->K * eb);
   p.dw = dw;
@@ -1105,26 +1077,20 @@ int wgrad_halo_try(const vk_conv_desc* d, const void* dz, float* dw, void* works
     if (d->dtype == VK_BF16) return launch_wh<bf16_t, 64, 32, false, true, 2>(p, workspace_bytes, st);
     return launch_wh<f16_t, 64, 32, false, true, 2>(p, workspace_bytes, st);
   }
-  switch (d->dtype) {
-    case VK_F32: return wh_select<float>(p, cgran, workspace_bytes, st);
-    case VK_BF16: return wh_select<bf16_t>(p, cgran, workspace_bytes, st);
-    case VK_F16: return wh_select<f16_t>(p, cgran, workspace_bytes, st);
-  }
-  return VK_ERR_ARG;
+  return dispatch_dtype(d->dtype, [&](auto e) { return wh_select<decltype(e)>(p, cgran, workspace_bytes, st); });
 }
 
 // ------------------------------------------------------------------------------------------------ batched launch (see wgrad_halo_batch_kernel)
-// would wgrad_halo_try run this layer on the 64 x 64 tap-split tile kernel (16-bit, 3x3 stride 1, K >= 64, every source a multiple of
-// 64 channels)?  Those are the layers a batch may hold.
+// would wgrad_halo_try run this 3x3 stride-1 layer on the 64 x 64 tap-split tile kernel (wh64_class)?  Those are the layers a batch may
+// hold.
 bool wgrad_batch_supports(const vk_conv_desc* d) {
   if (d->dtype == VK_F32 || d->R != 3 || d->S != 3 || d->pad != 1 || d->stride != 1 || d->H != d->Ho || d->W != d->Wo) return false;
-  if (getenv("VK_NO_WGRAD_HALO") || getenv("VK_WH_NO_TS") || getenv("VK_WH_NO_SLAB") || getenv("VK_NO_WGRAD_BATCH")) return false;
+  if (getenv("VK_NO_WGRAD_HALO") || getenv("VK_WH_NO_SLAB") || getenv("VK_NO_WGRAD_BATCH")) return false;
   WhParams p;
   int cgran;
   if (make_wh_params(d, d->src0.ptr, nullptr, &p, &cgran) != VK_OK) return false;
-  if (p.K < 64 || cgran % 64) return false;
-  const int kt = (p.K + 63) / 64, ct = p.C / 64;
-  return kt * ct <= wh_max_combo();
+  if (wh64_class(2, p.K, cgran) != Wh64::TAP_SPLIT) return false;
+  return wh_combo_ok((p.K + 63) / 64, p.C / 64);
 }
 
 
@@ -1216,28 +1182,18 @@ int wgrad_batch_launch(vk_dtype dt, const WgradBatchPlan& plan, const void* tabl
   VK_CHECK_ARG(dt != VK_F32 && plan.nwg > 0 && slab && plan.slab_need <= slab_bytes, "wgrad batch: slab of %zu bytes needed, %zu given",
                plan.slab_need, slab_bytes);
   using Cfg = WhCfg<bf16_t, 64, 64, false, true, 1>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    VK_CHECK_HIP(hipFuncSetAttribute((const void*)wgrad_halo_batch_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::SMEM));
-    VK_CHECK_HIP(hipFuncSetAttribute((const void*)wgrad_halo_batch_kernel<f16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::SMEM));
-    attr_done = true;
-  }
+  static_assert(Cfg::SMEM > 64 * 1024, "the batch kernel needs the dynamic-LDS attribute");
   const char* tb = (const char*)tables;
-  {
-    vkh::ProfScope ps("wgrad_halo_16b_64x64ts_batch", st, plan.flops, plan.bytes);
-    if (dt == VK_BF16)
-      hipLaunchKernelGGL(wgrad_halo_batch_kernel<bf16_t>, dim3((unsigned)plan.nwg), dim3(512), Cfg::SMEM, st, (const WhParams*)(tb + plan.off_layers),
-                         (const WhSeg*)(tb + plan.off_segs), (const int*)(tb + plan.off_wgfirst), (float*)slab);
-    else
-      hipLaunchKernelGGL(wgrad_halo_batch_kernel<f16_t>, dim3((unsigned)plan.nwg), dim3(512), Cfg::SMEM, st, (const WhParams*)(tb + plan.off_layers),
-                         (const WhSeg*)(tb + plan.off_segs), (const int*)(tb + plan.off_wgfirst), (float*)slab);
-  }
-  {
-    vkh::ProfScope ps("wgrad_slab_reduce", st, 0.0, (double)plan.slab_need + 2.0 * plan.ntred * 64.0 * 9.0 * 64.0 * 4.0);
-    hipLaunchKernelGGL(k_wgrad_tile_reduce, dim3((unsigned)plan.ntred, 4), dim3(256), 0, st, (const WhTileRed*)(tb + plan.off_tred), (const float*)slab);
-  }
-  VK_CHECK_HIP(hipGetLastError());
-  return VK_OK;
+  auto batch = [&](auto e) {
+    return vkh::launch<wgrad_halo_batch_kernel<decltype(e)>>(dim3((unsigned)plan.nwg), dim3(512), Cfg::SMEM, st, "wgrad_halo_16b_64x64ts_batch", {}, plan.flops,
+                                                             plan.bytes, (const WhParams*)(tb + plan.off_layers), (const WhSeg*)(tb + plan.off_segs),
+                                                             (const int*)(tb + plan.off_wgfirst), (float*)slab);
+  };
+  const int rc = dt == VK_BF16 ? batch(bf16_t()) : batch(f16_t());
+  if (rc != VK_OK) return rc;
+  return vkh::launch<k_wgrad_tile_reduce>(dim3((unsigned)plan.ntred, 4), dim3(256), 0, st, "wgrad_slab_reduce", {}, 0.0,
+                                          (double)plan.slab_need + 2.0 * plan.ntred * 64.0 * 9.0 * 64.0 * 4.0, (const WhTileRed*)(tb + plan.off_tred),
+                                          (const float*)slab);
 }
 
 }  // namespace vk

@@ -920,6 +920,90 @@ int vk_subpix_refine(const vk_subpix_params* params, int batch, int h, int w, co
                      size_t record_stride, size_t box_offset, int valid_offset, const int32_t* counts, int max_components,
                      const double* affine, vk_subpix_quad* out, void* stream);
 
+/* Second-pass inference on one window per indentation (zoom.hip).  The first pass detects on the letterboxed
+ * map; for every detection one S x S window is cut from the uint8 source image at the finest scale that still shows the indentation
+ * whole, the caller segments, fits and refines there (vk_geom_*, vk_subpix_refine with the window's affine row), and vk_zoom_merge
+ * puts the result back into the first pass's slot, or keeps the first pass's record.
+ *
+ * Coordinates: source pixel i covers [i, i + 1) and has its centre at i + 0.5.  A window is (X0, Y0, s): the continuous coordinate of
+ * its top-left edge and s source pixels per output pixel.  Output pixel x has its centre at X0 + (x + 0.5) s, the source pixel
+ * coordinate u = X0 + (x + 0.5) s - 0.5; as an affine row of vk_subpix_refine that is inv_scale = s, ox = -(X0 + 0.5 s - 0.5) / s.
+ * All arithmetic below is IEEE float64 with contraction off, evaluated as written, left to right inside the parentheses.
+ *
+ * vk_zoom_windows.  records / record_stride / box_offset / valid_offset / counts / max_components: the first pass's records, read in
+ * place as vk_subpix_refine reads them.  affine: device double [batch][3] or NULL (0, 0, 1).  sizes: device int32 [batch][2] = (h, w)
+ * of the source images.  For slot t < min(max(counts[b], 0), max_components) with valid != 0, in ascending (b, t):
+ *   sx_q = (box[2 q] - ox) * inv, sy_q = (box[2 q + 1] - oy) * inv, q = 0 .. 3;  cx = (((sx_0 + sx_1) + sx_2) + sx_3) * 0.25, cy alike;
+ *   e = 0; for q = 0 .. 3: e = max(e, fabs(sx_q - cx)), then e = max(e, fabs(sy_q - cy));
+ *   raw = (margin * (2 * e)) / S;  s = raw; unless raw >= s_min: s = s_min, bit SCALE_CLAMPED_LO; if raw > s_max: s = s_max, bit
+ *   SCALE_CLAMPED_HI;  X0 = (cx + 0.5) - (S * s) * 0.5, Y0 alike;  bit CLIPPED unless X0 >= 0, Y0 >= 0, X0 + S * s <= w and
+ *   Y0 + S * s <= h.
+ * The first max_windows of them are written to windows[] in that order (no atomics: one workgroup scans the slots); *n_windows (device
+ * int32) = min(their number, max_windows).  Nothing else is written.  Host checks (VK_ERR_ARG before anything touches the stream): null
+ * or misaligned buffers, the record layout as in vk_subpix_refine, batch 1..65535, max_components 1..4096, S 1..16384,
+ * 0.25 <= s_min <= s_max <= 64, margin in [1, 8], max_windows 1..65535.
+ *
+ * vk_zoom_gather.  windows: device, n of them (1..65535).  images_host: n_images entries, checked on the host (ptr != 0, h, w 1..16384,
+ * stride >= 3 w) and copied to images_dev (device, n_images * sizeof(vk_zoom_image)) on the stream; uint8 BGR, row r of image m at
+ * ptr + r * stride.  out: device float32 [n][3][S][S], RGB planes.  The value of channel c of output pixel (x, y) is the mean of the
+ * piecewise-constant source image over the square of side f = max(s, 1) centred on the pixel's centre:
+ *   ax = (X0 + (x + 0.5) * s) - f * 0.5, bx = ax + f; taps i = floor(ax) .. floor(bx), weight wx_i = min(bx, i + 1) - max(ax, i); ay, by,
+ *   wy_j alike with Y0 and y.  row_j = sum over i ascending from 0.0 of wx_i * p[j][i][c]; total = sum over j ascending from 0.0 of
+ *   wy_j * row_j; value = total / (f * f).  p is pad_value where (i, j) lies outside the image.
+ * For s <= 1 this is bilinear interpolation, for s >= 1 the area average, at s = 1 with integer X0, Y0 the source pixel itself.  Then
+ * q = min(max((int)rint(value), 0), 255) and out = ((float)q / 255.f - mean) / std, the float32 expression of vk_letterbox_preprocess.
+ * A window with map outside 0 .. n_images - 1, s outside [0.25, 64] or fabs(X0), fabs(Y0) above 2^30 (a NaN included) gives pad_value
+ * everywhere.  One workgroup per 32 x 8 output tile of one window; every thread takes the sums of its pixel straight from memory.  Under
+ * VK_ZOOM_STAGED (flags; the form that measured slower and is kept as a cross-check) the tile's source footprint is staged in LDS as
+ * aligned dwords, the horizontal pass leaves row sums in LDS and the vertical pass reads them, unless the footprint does not fit the LDS
+ * (s above about 5): the same operations in the same order, the same bits.  Every tap is checked against h, w; every offset is 64-bit.
+ *
+ * vk_zoom_merge.  windows / n: as above, n >= 0 (host count).  records2 .. max_components2: the second pass's geometry records
+ * [n][max_components2] and counts2 [n]; quads2: its vk_subpix_quad [n][max_components2] (all three may be NULL when n == 0).  coarse:
+ * the first pass's vk_subpix_quad [batch][max_components]; counts: the first pass's.  For slot t of map b below
+ * min(max(counts[b], 0), max_components), the window k with (map, slot) = (b, t) is looked up (binary search: the windows are sorted).
+ * Candidates: u < min(max(counts2[k], 0), max_components2) with valid != 0 in the record and in quads2, whose int32 polygon contains the
+ * window centre: with P = (S, S) and the doubled corners A_q = 2 * box_q, the four cross products (A_q+1 - A_q) x (P - A_q) in int64 are
+ * all >= 0 or all <= 0 (a point on an edge is inside).  Target: the candidate of largest area, the lowest u on a tie.  out[b][t] is
+ * quads2[k][target] with label and area of coarse[b][t], and status ZOOMED, when a target exists (else NO_TARGET), none of its four
+ * flags has a bit of VK_ZOOM_FAIL_MASK (else REFINE_FAILED) and fabs(d_mean - coarse d_mean) <= agree * coarse d_mean (else DISAGREES);
+ * in every other case, and when there is no window (NO_WINDOW), out[b][t] = coarse[b][t].  status [batch][max_components] int32 is the
+ * case or-ed with the window's bits, scale [batch][max_components] double the window's s (0 without a window); both are written for
+ * every slot, NO_WINDOW and 0 from min(count, max_components) on, where out is not touched.  One thread per slot, no atomics, no
+ * workspace.  Host checks: as vk_zoom_windows, plus agree finite and >= 0. */
+#define VK_ZOOM_CLIPPED 1
+#define VK_ZOOM_SCALE_CLAMPED_LO 2
+#define VK_ZOOM_SCALE_CLAMPED_HI 4
+#define VK_ZOOM_ZOOMED 16
+#define VK_ZOOM_NO_TARGET 32
+#define VK_ZOOM_REFINE_FAILED 64
+#define VK_ZOOM_DISAGREES 128
+#define VK_ZOOM_NO_WINDOW 256
+#define VK_ZOOM_FAIL_MASK 0x7f   /* every VK_SUBPIX_* bit */
+#define VK_ZOOM_STAGED 1
+typedef struct vk_zoom_params {
+  int S, max_windows;
+  double margin, s_min, s_max;
+} vk_zoom_params;
+typedef struct vk_zoom_window {
+  int map, slot, status, pad;
+  double X0, Y0, s;
+} vk_zoom_window;
+typedef struct vk_zoom_image {
+  uint64_t ptr;                 /* device address of pixel (0, 0) */
+  int h, w;
+  int64_t stride;               /* bytes between rows, >= 3 w */
+} vk_zoom_image;
+int vk_zoom_windows(const vk_zoom_params* params, int batch, const void* records, size_t record_stride, size_t box_offset,
+                    int valid_offset, const int32_t* counts, int max_components, const double* affine, const int32_t* sizes,
+                    vk_zoom_window* windows, int32_t* n_windows, void* stream);
+int vk_zoom_gather(int n, int S, const vk_zoom_window* windows, int n_images, const vk_zoom_image* images_host, void* images_dev,
+                   int pad_value, int flags, float* out, void* stream);
+int vk_zoom_merge(int S, double agree, int n, const vk_zoom_window* windows, const void* records2, size_t record_stride2,
+                  size_t box_offset2, int valid_offset2, const int32_t* counts2, int max_components2, const vk_subpix_quad* quads2,
+                  int batch, int max_components, const int32_t* counts, const vk_subpix_quad* coarse, vk_subpix_quad* out,
+                  int32_t* status, double* scale, void* stream);
+
 /* AdamW (decoupled decay) over a flat fp32 parameter buffer; optionally emits the 16-bit working copy.
  * inv_scale multiplies the gradient first (GradScaler unscale / data-parallel averaging).
  * found_inf (optional int*): when *found_inf != 0 on the device the step is skipped: param, the moments and lowp_copy stay unwritten.

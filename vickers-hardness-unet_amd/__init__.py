@@ -10,7 +10,7 @@ Import by string (the directory name carries hyphens)::
     optimizer = vk.adamw_for(model, lr=5e-5, weight_decay=1e-4)
 
 Everything heavy runs in libvkunet.so (hand-written HIP); there is no CPU fallback."""
-from . import _lib, augment, averaging, encoders, geometry, instances, losses, lovasz, multiclass, parallel, patches, prepost, seglosses, segmetrics, subpix, sweep, synthetic, tiling  # noqa: F401
+from . import _lib, augment, averaging, encoders, geometry, instances, losses, lovasz, multiclass, parallel, patches, prepost, seglosses, segmetrics, subpix, sweep, synthetic, tiling, zoom  # noqa: F401
 from .augment import AugmentSampler, DeviceDataset  # noqa: F401
 from .averaging import SWA, ModelEMA  # noqa: F401
 from .patches import PatchDataset, PatchSampler  # noqa: F401
@@ -21,6 +21,7 @@ from .losses import BCEDiceLoss, DiceLoss  # noqa: F401
 from .segmetrics import dice_coef, iou_coef, seg_metrics, seg_metrics_device  # noqa: F401
 from .instances import Detections, MatchResult, ObjectMetrics, object_metrics  # noqa: F401
 from .subpix import RefinedDetections  # noqa: F401
+from .zoom import ZoomedDetections  # noqa: F401
 from .sweep import SweepResult, ThresholdSweep, sweep_curves, sweep_hist, threshold_sweep  # noqa: F401
 from .optim import FusedAdamW, GradScaler, adamw_for, clip_grad_norm_, finetune_groups  # noqa: F401
 from .parallel import GradientReducer, all_reduce_scalars, broadcast_model, make_data_parallel  # noqa: F401
@@ -35,4 +36,5 @@ __all__ = ["Unet", "build_model", "DiceLoss", "BCEDiceLoss", "multiclass", "enco
            "sweep", "ThresholdSweep", "SweepResult", "threshold_sweep", "sweep_hist", "sweep_curves",
            "instances", "ObjectMetrics", "object_metrics", "Detections", "MatchResult",
            "subpix", "RefinedDetections",
+           "zoom", "ZoomedDetections",
            "averaging", "ModelEMA", "SWA"]

@@ -138,6 +138,25 @@ class vk_subpix_quad(C.Structure):
                 ("d_mean", C.c_double)]
 
 
+ZOOM_STATUS = {"clipped": 1, "scale_clamped_lo": 2, "scale_clamped_hi": 4, "zoomed": 16, "no_target": 32, "refine_failed": 64,
+               "disagrees": 128, "no_window": 256}
+VK_ZOOM_FAIL_MASK = 0x7F
+VK_ZOOM_STAGED = 1
+
+
+class vk_zoom_params(C.Structure):
+    _fields_ = [("S", C.c_int), ("max_windows", C.c_int), ("margin", C.c_double), ("s_min", C.c_double), ("s_max", C.c_double)]
+
+
+class vk_zoom_window(C.Structure):
+    _fields_ = [("map", C.c_int), ("slot", C.c_int), ("status", C.c_int), ("pad", C.c_int), ("X0", C.c_double), ("Y0", C.c_double),
+                ("s", C.c_double)]
+
+
+class vk_zoom_image(C.Structure):
+    _fields_ = [("ptr", C.c_uint64), ("h", C.c_int), ("w", C.c_int), ("stride", C.c_int64)]
+
+
 class vk_adamw_group(C.Structure):
     _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float)]
 
@@ -254,6 +273,9 @@ SIGNATURES = {
     "vk_inst_contingency": (ci, [ci, ci, ci, vp, vp, ci, ci, vp, vp]),
     "vk_inst_match": (ci, [ci, ci, ci, vp, vp, vp, ci, vp, vp, sz, vp, sz, vp, vp, vp, vp, vp, ci, vp]),
     "vk_subpix_refine": (ci, [P(vk_subpix_params), ci, ci, ci, vp, vp, sz, sz, ci, vp, ci, vp, vp, vp]),
+    "vk_zoom_windows": (ci, [P(vk_zoom_params), ci, vp, sz, sz, ci, vp, ci, vp, vp, vp, vp, vp]),
+    "vk_zoom_gather": (ci, [ci, ci, vp, ci, P(vk_zoom_image), vp, ci, ci, vp, vp]),
+    "vk_zoom_merge": (ci, [ci, cd, ci, vp, vp, sz, sz, ci, vp, ci, vp, ci, ci, vp, vp, vp, vp, vp, vp]),
     "vk_adamw_step": (ci, [sz, vp, vp, vp, vp, cf, cf, cf, cf, cf, ci, cf, vp, vp, ci, vp]),
     "vk_amp_check_inf": (ci, [sz, vp, vp, vp]),
     "vk_amp_unscale_check": (ci, [sz, vp, vp, vp, vp]),

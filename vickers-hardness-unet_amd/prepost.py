@@ -156,6 +156,15 @@ class Segmenter:
         out = run_tiled(self.model, img_bgr, self.img_size if tile is None else tile, overlap, tta, blend, batch, device=self.device)
         return (out[0] if out.shape[0] == 1 else out).cpu().numpy()
 
+    def measure(self, img_bgr: np.ndarray, fit: str = "quad", zoom: bool = True, **kw) -> List[dict]:
+        """The indentations of one image, measured in source pixels: letterbox -> model -> ``vk.geometry.detect`` -> sub-pixel
+        refinement with the letterbox's affine row, then (``zoom=True``) the second pass of ``vk.zoom``: one window per detection cut
+        from the image at the finest scale that shows it whole, segmented, fitted and refined there.  Returns the detection list of
+        ``vk.subpix.postprocess`` (sorted by area; ``d1``, ``d2``, ``d_mean``, ``box_subpix`` in source pixels), with ``zoom_status``
+        and ``zoom_scale`` per row after the zoom pass.  ``kw``: ``method`` and the arguments of ``vk.zoom.refine_detections``."""
+        from .zoom import measure
+        return measure(self, img_bgr, fit=fit, zoom=zoom, **kw)
+
     def infer_batch(self, images: Sequence[np.ndarray]) -> List[np.ndarray]:
         """Several images through ONE forward pass (the reference runs them one by one)."""
         x, metas = preprocess_batch(images, self.img_size, "centered", self.device)

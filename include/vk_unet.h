@@ -1004,6 +1004,128 @@ int vk_zoom_merge(int S, double agree, int n, const vk_zoom_window* windows, con
                   int batch, int max_components, const int32_t* counts, const vk_subpix_quad* coarse, vk_subpix_quad* out,
                   int32_t* status, double* scale, void* stream);
 
+/* Validation panels and detection overlays (render.hip): the last stage of the reference's three programs, the
+ * drawing of what was measured, without leaving the device.  Everything below is integer arithmetic or float arithmetic in a fixed
+ * order with contraction off, so a restatement from this text gives the same bytes (tests/render_ref.py).  The thick-line rule, the
+ * font and the absence of antialiasing are this library's own; they are not OpenCV's.  No kernel uses atomics or a workspace; every
+ * read and write is checked against the sizes given, every byte offset is 64-bit.  All host checks return VK_ERR_ARG before anything
+ * touches the stream.
+ *
+ * The blend of a base byte a and an overlay byte c (vk_render_blend: colour BGR, alpha the weight of the base, beta of the overlay):
+ *   q = sat_u8(rint(((float)a * alpha + (float)c * beta) + gamma)): float32, every operation rounded on its own, rint to nearest with
+ *   ties to even, then 0 for r <= 0 and 255 for r >= 255.  This is the definition cv2.addWeighted documents for 8-bit images.  alpha,
+ *   beta and gamma lie in [-1e6, 1e6].
+ *
+ * vk_render_val_panels: train.py's four-panel image.  x: device float32 [N][3][H][W] (RGB planes, normalised), y and prob: float32
+ * [N][1][H][W]; mean, std: host double[3], |.| <= 1e6; N 1..65535, H, W 1..16384.  out: device uint8, row r of image n at
+ * out + (n * H + r) * row_stride, row_stride >= 12 W (and <= 2^31); a row holds four panels of W pixels of three bytes, bytes from 12 W
+ * on are never written.  Panel 0: per RGB plane k, v = (((double)x * std[k]) + mean[k]) * 255.0 in float64 as written; the byte is 0
+ * unless v > 0 (so for a NaN), 255 for v >= 255, else (int)v (truncation); stored B, G, R.  Panel 1: p = y * 255.f in float32; 0 unless
+ * p > 0, 255 for p >= 255.f, else (int)p; three times.  Panel 2: the same from prob.  Panel 3: per channel the blend of panel 0's
+ * byte with blend.color where panel 2's byte is > 127, with 0 elsewhere.  Under VK_RENDER_RGB (flags) the three bytes of every pixel
+ * of every panel are stored in the reverse order.
+ *
+ * vk_render_primitives: the drawing list, from the records in place.  records / record_stride / valid_offset / counts /
+ * max_components / affine: as in vk_subpix_refine, but record_stride is a multiple of 8 and records is 8-byte aligned.  diag_offset: a
+ * double (d_mean) in the record.  coord_mode and box_offset: VK_RENDER_COORD_BOX: int32 box[8] at box_offset and float cx, cy at
+ * center_offset; VK_RENDER_COORD_V: double v[8] at box_offset; VK_RENDER_COORD_VS: double vs[8] at box_offset, which are source
+ * coordinates already: the affine row is not applied.  center_offset is read in BOX mode only.  With (ox, oy, inv) the affine row, or
+ * (0, 0, 1): m_x = ((double)c_x - ox) * inv, m_y = ((double)c_y - oy) * inv for the four corners and, in BOX mode, for (cx, cy); in the
+ * other modes cx = (((m_x0 + m_x1) + m_x2) + m_x3) * 0.25, cy alike.  A slot t < min(max(counts[b], 0), max_components) with
+ * valid != 0 is skipped (counted in skipped[b], takes no part in what follows) unless fabs of all eight m and of cx, cy is
+ * <= VK_RENDER_MAX_COORD = 2^20 (a NaN fails); otherwise it is drawn: corner = (int32)rint(m) (ties to even), anchor =
+ * ((int)cx + 6, (int)cy - 6) (truncation).
+ *   rank = the number of drawn slots u of the map with area_u > area_t, or area_u == area_t and u < t (area: the int at byte 4);
+ *   idx = rank + 1, the number detections.sort(key=area, reverse=True) gives.  color = palette[rank % 8].
+ *   diag = (i1, j1, i2, j2): among the pairs (0,1) (0,2) (0,3) (1,2) (1,3) (2,3) of corners the first one of largest squared distance
+ *   in int64, and the other two corners ascending.
+ *   label = "#<idx> mean=<D>px", D = the digits of printf("%.1f", d_mean) for 0 <= d_mean < 1e6, else "?":  hi = d * 10.0,
+ *   lo = fma(d, 10.0, -hi), f = floor(hi), r = ((hi - f) - 0.5) + lo; n = f + 1 when r > 0, f when r < 0, the even one of the two when
+ *   r == 0; D = n / 10, '.', n % 10.  (-0.0 prints 0.0.)  label_len characters, the rest of label[] is 0.
+ *   bbox = (x0, y0, x1, y1), inclusive, with p = (thickness + 1) / 2 and L = label_len: x0 = min(min corner x - p, anchor x),
+ *   y0 = min(min corner y - p, anchor y - 7 text_scale + 1), x1 = max(max corner x + p, anchor x + 6 text_scale L - 1),
+ *   y1 = max(max corner y + p, anchor y).
+ * prims: device vk_render_prim [batch][max_components], 8-byte aligned; the record of rank r of map b is written to prims[b][r], every
+ * byte of it (pad = 0); drawn[b] = their number, skipped[b]: device int32 [batch].  Nothing else is written.  Host checks: null or
+ * misaligned buffers, batch 1..65535, max_components 1..4096, the offsets inside the record and aligned, thickness and text_scale 1..8.
+ *
+ * vk_render_draw: views_host: batch entries of vk_render_view, checked on the host (h, w 1..16384; src, mask != 0; every stride at
+ * least its row and <= 2^31; a float mask 4-byte aligned; at least one output) and copied to views_dev (device, 8-byte aligned,
+ * batch * sizeof(vk_render_view)) on the stream.  src: uint8 BGR, row r at src + r * src_stride.  mask: VK_RENDER_MASK_U8: uint8,
+ * foreground where != 0; VK_RENDER_MASK_F32: float32, foreground where value > thresh in float32.  out[0] (vis_o): the source.  out[1]
+ * (vis_b): 255 on the foreground, 0 elsewhere, three times.  out[2] (vis_v): per channel the blend of the source byte with blend.color on
+ * the foreground and with 0 elsewhere.  An output address of 0 is not wanted.  prims / drawn / max_components: the list of
+ * vk_render_primitives, or NULL for none; the first min(max(drawn[b], 0), max_components) records of map b are painted over every
+ * output in list order, per record the four sides (0-1, 1-2, 2-3, 3-0) in color, then the two diagonals in diag_color, then the label in
+ * color: per pixel the last one that covers it wins.  A record is not painted at all unless thickness and text_scale are 1..8, label_len
+ * <= 24, every diag index < 4, every corner within +-2^20 and the anchor within +-2^21; and only inside its bbox.
+ *   Segment A-B at thickness t covers pixel P iff 4 * dist^2(P, segment) <= t^2, in integers: d = B - A, e = P - A, L = d.d, u = e.d;
+ *   if L == 0 or u <= 0: 4 e.e <= t^2; else if u >= L: 4 |P - B|^2 <= t^2; else 4 * cross(d, e)^2 <= t^2 * L, cross = d.x e.y - d.y e.x.
+ *   With corners within +-2^20 and pixels in 0..16383: |d| components <= 2^21, |e| < 2^21, so L <= 2^43, |u| and |cross| < 2^44 and
+ *   4 e.e < 2^45 fit int64; t^2 L <= 2^49, so a |cross| >= 2^26 cannot satisfy the test and is refused before it is squared, and
+ *   4 cross^2 < 2^54 otherwise.
+ *   Text: with s = text_scale, u = P.x - anchor.x, v = P.y - (anchor.y - 7 s + 1): inside when 0 <= u < 6 s label_len and 0 <= v < 7 s;
+ *   cell = u / s, row = v / s, character k = cell / 6, column c = cell % 6; covered when c < 5 and bit (4 - c) of row `row` of the glyph of
+ *   label[k] (vk_render_glyph) is set.  The anchor is the bottom-left pixel of the text.  A character without a glyph paints nothing.
+ * One workgroup per 32 x 8 tile of one map tests the records' bboxes against its tile and keeps the hits in LDS in list order (ballot and
+ * prefix count), then every pixel walks that list from its end; under VK_RENDER_DIRECT (flags; the form that measured slower, kept as a
+ * cross-check) every pixel walks the whole list: the same bytes.
+ *
+ * vk_render_reduce: src uint8 [h][w][3] with src_stride -> dst [ceil(h / k)][ceil(w / k)][3] with dst_stride, k 1..16; per channel
+ * (sum + n / 2) / n in integers over the n source pixels of the block (rows k Y .. min(k Y + k, h) - 1, columns alike).
+ *
+ * vk_render_glyph: host only; rows[7] of the 5 x 7 glyph of ch, top row first, bit 4 the left column; VK_ERR_ARG for a character the
+ * label cannot contain (it contains "#0123456789 mean=.px?"). */
+#define VK_RENDER_RGB 1
+#define VK_RENDER_DIRECT 1
+#define VK_RENDER_MASK_U8 0
+#define VK_RENDER_MASK_F32 1
+#define VK_RENDER_COORD_BOX 0
+#define VK_RENDER_COORD_V 1
+#define VK_RENDER_COORD_VS 2
+#define VK_RENDER_MAX_COORD 1048576
+#define VK_RENDER_LABEL_MAX 24
+typedef struct vk_render_blend {
+  uint8_t color[3];             /* B, G, R */
+  uint8_t pad;
+  float alpha, beta, gamma;
+} vk_render_blend;
+typedef struct vk_render_style {
+  uint8_t palette[8][3];        /* B, G, R */
+  uint8_t diag[3];
+  uint8_t pad;
+  int thickness, text_scale;    /* 1..8 each */
+} vk_render_style;
+typedef struct vk_render_prim {
+  int32_t rank, slot;
+  int32_t corner[8];            /* x0,y0 .. x3,y3 on the image that is drawn on */
+  int32_t anchor[2];
+  int32_t bbox[4];              /* x0, y0, x1, y1, inclusive */
+  uint8_t diag[4];              /* i1, j1, i2, j2 */
+  uint8_t color[3], label_len;
+  uint8_t diag_color[3], thickness;
+  uint8_t text_scale, pad[3];
+  char label[VK_RENDER_LABEL_MAX];
+} vk_render_prim;
+typedef struct vk_render_view {
+  uint64_t src;                 /* device addresses; 0 in out[] = not wanted */
+  int64_t src_stride;
+  uint64_t mask;
+  int64_t mask_stride;          /* bytes */
+  uint64_t out[3];              /* vis_o, vis_b, vis_v */
+  int64_t out_stride[3];
+  int h, w;
+} vk_render_view;
+int vk_render_val_panels(int N, int H, int W, const float* x, const float* y, const float* prob, const double* mean, const double* stdv,
+                         const vk_render_blend* blend, int flags, uint8_t* out, int64_t row_stride, void* stream);
+int vk_render_primitives(int batch, const void* records, size_t record_stride, size_t box_offset, int valid_offset, int diag_offset,
+                         int center_offset, int coord_mode, const int32_t* counts, int max_components, const double* affine,
+                         const vk_render_style* style, vk_render_prim* prims, int32_t* drawn, int32_t* skipped, void* stream);
+int vk_render_draw(int batch, const vk_render_view* views_host, void* views_dev, int mask_kind, float thresh, const vk_render_blend* blend,
+                   const vk_render_prim* prims, const int32_t* drawn, int max_components, int flags, void* stream);
+int vk_render_reduce(int h, int w, int k, const uint8_t* src, int64_t src_stride, uint8_t* dst, int64_t dst_stride, void* stream);
+int vk_render_glyph(int ch, uint8_t rows[7]);
+
 /* AdamW (decoupled decay) over a flat fp32 parameter buffer; optionally emits the 16-bit working copy.
  * inv_scale multiplies the gradient first (GradScaler unscale / data-parallel averaging).
  * found_inf (optional int*): when *found_inf != 0 on the device the step is skipped: param, the moments and lowp_copy stay unwritten.

@@ -157,6 +157,34 @@ class vk_zoom_image(C.Structure):
     _fields_ = [("ptr", C.c_uint64), ("h", C.c_int), ("w", C.c_int), ("stride", C.c_int64)]
 
 
+VK_RENDER_RGB = 1
+VK_RENDER_DIRECT = 1
+VK_RENDER_MASK_U8, VK_RENDER_MASK_F32 = 0, 1
+VK_RENDER_COORD_BOX, VK_RENDER_COORD_V, VK_RENDER_COORD_VS = 0, 1, 2
+VK_RENDER_MAX_COORD = 1 << 20
+VK_RENDER_LABEL_MAX = 24
+RENDER_CHARS = "#0123456789 mean=.px?"
+
+
+class vk_render_blend(C.Structure):
+    _fields_ = [("color", C.c_uint8 * 3), ("pad", C.c_uint8), ("alpha", C.c_float), ("beta", C.c_float), ("gamma", C.c_float)]
+
+
+class vk_render_style(C.Structure):
+    _fields_ = [("palette", (C.c_uint8 * 3) * 8), ("diag", C.c_uint8 * 3), ("pad", C.c_uint8), ("thickness", C.c_int), ("text_scale", C.c_int)]
+
+
+class vk_render_prim(C.Structure):
+    _fields_ = [("rank", C.c_int32), ("slot", C.c_int32), ("corner", C.c_int32 * 8), ("anchor", C.c_int32 * 2), ("bbox", C.c_int32 * 4),
+                ("diag", C.c_uint8 * 4), ("color", C.c_uint8 * 3), ("label_len", C.c_uint8), ("diag_color", C.c_uint8 * 3),
+                ("thickness", C.c_uint8), ("text_scale", C.c_uint8), ("pad", C.c_uint8 * 3), ("label", C.c_uint8 * VK_RENDER_LABEL_MAX)]
+
+
+class vk_render_view(C.Structure):
+    _fields_ = [("src", C.c_uint64), ("src_stride", C.c_int64), ("mask", C.c_uint64), ("mask_stride", C.c_int64), ("out", C.c_uint64 * 3),
+                ("out_stride", C.c_int64 * 3), ("h", C.c_int), ("w", C.c_int)]
+
+
 class vk_adamw_group(C.Structure):
     _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float)]
 
@@ -276,6 +304,11 @@ SIGNATURES = {
     "vk_zoom_windows": (ci, [P(vk_zoom_params), ci, vp, sz, sz, ci, vp, ci, vp, vp, vp, vp, vp]),
     "vk_zoom_gather": (ci, [ci, ci, vp, ci, P(vk_zoom_image), vp, ci, ci, vp, vp]),
     "vk_zoom_merge": (ci, [ci, cd, ci, vp, vp, sz, sz, ci, vp, ci, vp, ci, ci, vp, vp, vp, vp, vp, vp]),
+    "vk_render_val_panels": (ci, [ci, ci, ci, vp, vp, vp, P(cd), P(cd), P(vk_render_blend), ci, vp, i64, vp]),
+    "vk_render_primitives": (ci, [ci, vp, sz, sz, ci, ci, ci, ci, vp, ci, vp, P(vk_render_style), vp, vp, vp, vp]),
+    "vk_render_draw": (ci, [ci, P(vk_render_view), vp, ci, cf, P(vk_render_blend), vp, vp, ci, ci, vp]),
+    "vk_render_reduce": (ci, [ci, ci, ci, vp, i64, vp, i64, vp]),
+    "vk_render_glyph": (ci, [ci, P(C.c_uint8)]),
     "vk_adamw_step": (ci, [sz, vp, vp, vp, vp, cf, cf, cf, cf, cf, ci, cf, vp, vp, ci, vp]),
     "vk_amp_check_inf": (ci, [sz, vp, vp, vp]),
     "vk_amp_unscale_check": (ci, [sz, vp, vp, vp, vp]),

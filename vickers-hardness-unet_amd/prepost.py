@@ -165,6 +165,14 @@ class Segmenter:
         from .zoom import measure
         return measure(self, img_bgr, fit=fit, zoom=zoom, **kw)
 
+    def render(self, img_bgr: np.ndarray, fit: str = "quad", zoom: bool = True, reduce: int = 1, **kw):
+        """``measure`` plus what the GUIs show: the image, the binary map and the overlay, each with every detection's box, diagonals
+        and ``#<n> mean=<d>px`` drawn on the device (``vk.render``, with the refined source-pixel vertices) -> (detection list, vis_o,
+        vis_b, vis_v), numpy uint8 [h, w, 3], or [ceil(h / reduce), ceil(w / reduce), 3] after a box reduction on the device.  ``kw``:
+        ``thickness``, ``text_scale``, and the arguments of ``measure``."""
+        from .render import render
+        return render(self, img_bgr, fit=fit, zoom=zoom, reduce=reduce, **kw)
+
     def infer_batch(self, images: Sequence[np.ndarray]) -> List[np.ndarray]:
         """Several images through ONE forward pass (the reference runs them one by one)."""
         x, metas = preprocess_batch(images, self.img_size, "centered", self.device)

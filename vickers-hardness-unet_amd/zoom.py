@@ -223,20 +223,28 @@ def postprocess(segment: Callable, images: Sequence[torch.Tensor], prob: torch.T
     return dets.clean, _lists(dets, fine, fit)
 
 
-def measure(seg, img_bgr, fit: str = "quad", zoom: bool = True, method: str = "corner", **kw) -> List[Dict]:
-    """``Segmenter.measure``: letterbox -> model -> detect -> coarse refinement with the letterbox's affine row (-> the zoom pass) -> the
-    detection list of one image in source pixels.  ``kw`` go to ``refine_detections``."""
+def _measure(seg, img_bgr, fit: str, zoom: bool, method: str, **kw):
+    """The steps of ``measure`` -> (the image on the device, the letterbox metadata, the logits [S, S], the first pass's detections, the
+    refined ones)."""
     from . import prepost as PP
     src = PP._as_device_u8(img_bgr, seg.device)
     h, w = int(src.shape[0]), int(src.shape[1])
     size = int(seg.img_size)
     with torch.no_grad():
-        x, _ = PP.preprocess(src, size, "centered", seg.device)
-        prob = torch.sigmoid(seg.model(x)[:, 0].float())
+        x, meta = PP.preprocess(src, size, "centered", seg.device)
+        logits = seg.model(x)[:, 0].float()
+        prob = torch.sigmoid(logits)
     dets = G.detect(prob, fit=fit)
     aff = SP.letterbox_affine(h, w, size, "centered")
     if zoom:
         fine = refine_detections(seg.model, [src], dets, prob, affine=aff, S=size, method=method, **kw)
     else:
         fine = SP.refine(dets, prob, method=method, affine=aff, **(kw.get("refine_args") or {}))
+    return src, meta, logits[0], dets, fine
+
+
+def measure(seg, img_bgr, fit: str = "quad", zoom: bool = True, method: str = "corner", **kw) -> List[Dict]:
+    """``Segmenter.measure``: letterbox -> model -> detect -> coarse refinement with the letterbox's affine row (-> the zoom pass) -> the
+    detection list of one image in source pixels.  ``kw`` go to ``refine_detections``."""
+    _, _, _, dets, fine = _measure(seg, img_bgr, fit, zoom, method, **kw)
     return _lists(dets, fine, fit)[0]

@@ -40,6 +40,8 @@
  *   vk_letterbox_u8 / _mask_u8 / vk_augment_batch  VickersDataset.__getitem__ + albumentations pipeline  train.py:67-113, 173-200
  *   vk_patch_index / vk_patch_batch ........... random S x S training patches of the full-resolution images (no counterpart: the
  *                                               reference trains on letterboxed images only)
+ *   vk_cp_boxes / vk_cp_alpha / vk_cp_paste ... instance copy-paste between the letterboxed items (no counterpart: the reference never
+ *                                               composes images)
  *
  * Conventions
  *   - plain pointers and sizes only; no C++/torch types cross this boundary.
@@ -513,6 +515,50 @@ int vk_patch_index(int n_items, const vk_patch_item* items_host, void* items_dev
 int vk_patch_batch(int n, int size, int n_items, const void* items_dev, const uint8_t* images, const uint8_t* masks, const int32_t* rowcum,
                    const vk_patch_params* params_host, void* params_dev, int flags, int32_t* origins, uint8_t* patches_rgb,
                    uint8_t* patches_mask, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Instance copy-paste: a compose step between the letterboxed uint8 store of vk_letterbox_u8 / _mask_u8 and
+ * vk_augment_batch.  All arithmetic is integer: the results are bytes a numpy restatement gives again (tests/copypaste_ref.py).
+ *
+ * vk_cp_boxes: slots int32 [batch][h][w] as vk_geom_slot_map writes it -> boxes int32 [batch][max_slots][5] = x0, y0, x1, y1
+ * (inclusive), area of every slot 0 <= s < max_slots; an empty slot gives (w, h, -1, -1, 0).  Negative slots and slots >= max_slots
+ * are ignored.  The call initialises boxes itself.  Per wave, then per workgroup (LDS), then integer min / max / add atomics on
+ * boxes: no order to depend on.  batch 1..65535, h, w 1..16384, max_slots 1..256.
+ *
+ * vk_cp_alpha: kept = (slot >= 0) and alpha, uint8 [batch][h][w] each.  acc = sum over dy, dx in -3..3 of b[dy] b[dx] kept(y + dy,
+ * x + dx), b = (1, 6, 15, 20, 15, 6, 1), taps outside the map 0, so acc is in 0..4096; alpha = min(255, (acc * 2040 + 2048) >> 12): a
+ * gain of 8 — 255 from one eighth of the full sum on, 0 beyond Chebyshev distance 3 of every kept pixel.
+ *
+ * vk_cp_paste: the stores are uint8, images_rgb [n_items][S][S][3] and masks, kept, alpha [n_items][S][S] (masks in {0, 1}).  Sample k
+ * of n starts as a copy of item base_index_dev[k] (device int32 [n], clamped to the store as vk_augment_batch clamps its index) and
+ * takes the counts_host[k] <= VK_CP_MAX_PASTES records recs_host[k][0 ..] in list order (recs_host: host [n][VK_CP_MAX_PASTES], every
+ * entry readable).  recs_dev: device scratch of VK_CP_RECS_DEV_BYTES(n), 4-byte aligned: the records, then the counts.
+ *   T = rot90(P[:, ::-1] if d4 & 4 else P, d4 & 3) (counter-clockwise quarter turns, numpy's rot90) of the donor box P of a map of
+ *   item `donor`, th x tw.  For column i and row j of the destination box: U = ((2 i + 1) * tw * 256) / (2 dw) - 128 clipped to
+ *   [0, (tw - 1) * 256], V likewise from j, th, dh; x0 = U >> 8, fx = U & 255, x1 = min(x0 + 1, tw - 1), y alike.  Per colour channel and
+ *   for alpha: top = p00 (256 - fx) + p01 fx, bot = p10 (256 - fx) + p11 fx, val = (top (256 - fy) + bot fy + 32768) >> 16.
+ *   k = T_kept[min((V + 128) >> 8, th - 1)][min((U + 128) >> 8, tw - 1)].  Then, a being the alpha value, per channel
+ *   cur = (a val + (255 - a) cur + 127) / 255 and m |= k.  Pixels of the box outside the image are dropped.
+ * Every pixel of out_rgb [n][S][S][3] and out_mask [n][S][S] is written exactly once and depends on the stores alone: no atomics, no
+ * workspace but recs_dev.  Host checks (VK_ERR_ARG before anything touches the stream): n 1..65535, S 1..4096, n_items >= 1, no null
+ * buffer, stores / outputs / recs_dev 4-byte aligned, counts in 0..VK_CP_MAX_PASTES, and per used record: donor in 0..n_items-1, the
+ * donor box inside [0, S) with sw, sh >= 1, d4 in 0..7, dw, dh in 1..2S, dx0, dy0 in [-2S, 2S].
+ * ---------------------------------------------------------------------------------------------- */
+#define VK_CP_MAX_PASTES 8
+#define VK_CP_MAX_SLOTS 256
+#define VK_CP_MAX_SIDE 4096
+typedef struct vk_cp_rec {
+  int32_t donor;                /* item of the stores the instance is taken from */
+  int32_t sx0, sy0, sw, sh;     /* donor box */
+  int32_t d4;                   /* bit 2: mirror the columns first; bits 0-1: counter-clockwise quarter turns */
+  int32_t dx0, dy0, dw, dh;     /* destination box; may leave the image */
+} vk_cp_rec;
+#define VK_CP_RECS_DEV_BYTES(n) ((size_t)(n) * (VK_CP_MAX_PASTES * sizeof(vk_cp_rec) + sizeof(int32_t)))
+int vk_cp_boxes(int batch, int h, int w, const int32_t* slots, int max_slots, int32_t* boxes, void* stream);
+int vk_cp_alpha(int batch, int h, int w, const int32_t* slots, uint8_t* kept, uint8_t* alpha, void* stream);
+int vk_cp_paste(int n, int S, int n_items, const uint8_t* images_rgb, const uint8_t* masks, const uint8_t* kept, const uint8_t* alpha,
+                const int32_t* base_index_dev, const int32_t* counts_host, const vk_cp_rec* recs_host, void* recs_dev, uint8_t* out_rgb,
+                uint8_t* out_mask, void* stream);
 
 /* NCHW fp32 [N][3][H][W] -> NHWC4 `dtype` */
 int vk_input_transform(vk_dtype dtype, int N, int H, int W, const float* x, void* x4, void* stream);

@@ -86,6 +86,18 @@ class vk_patch_params(C.Structure):
                 ("sin_a", C.c_float), ("reserved", C.c_int)]
 
 
+VK_CP_MAX_PASTES, VK_CP_MAX_SLOTS, VK_CP_MAX_SIDE = 8, 256, 4096
+CP_REC_FIELDS = ("donor", "sx0", "sy0", "sw", "sh", "d4", "dx0", "dy0", "dw", "dh")
+
+
+class vk_cp_rec(C.Structure):
+    _fields_ = [(f, C.c_int32) for f in CP_REC_FIELDS]
+
+
+def vk_cp_recs_dev_bytes(n: int) -> int:
+    return n * (VK_CP_MAX_PASTES * C.sizeof(vk_cp_rec) + 4)
+
+
 class vk_seg_loss_cfg(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("terms", C.c_uint32), ("has_ignore", C.c_int32),
                 ("ignore_index", C.c_int32), ("w_pix", C.c_float), ("w_focal", C.c_float), ("w_dice", C.c_float),
@@ -260,6 +272,9 @@ SIGNATURES = {
     "vk_augment_batch": (ci, [ci, ci, ci, vp, vp, vp, P(vk_aug_params), vp, vp, vp, C.c_size_t, vp, vp, vp]),
     "vk_patch_index": (ci, [ci, P(vk_patch_item), vp, sz, vp, sz, vp, sz, vp]),
     "vk_patch_batch": (ci, [ci, ci, ci, vp, vp, vp, vp, P(vk_patch_params), vp, ci, vp, vp, vp, vp]),
+    "vk_cp_boxes": (ci, [ci, ci, ci, vp, ci, vp, vp]),
+    "vk_cp_alpha": (ci, [ci, ci, ci, vp, vp, vp, vp]),
+    "vk_cp_paste": (ci, [ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "vk_input_transform": (ci, [ci, ci, ci, ci, vp, vp, vp]),
     "vk_bn_finalize": (ci, [ci, ci, vp, cd, vp, vp, vp, vp, cf, cf, vp, vp, vp, vp, vp]),
     "vk_bn_relu_maxpool": (ci, [ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]),

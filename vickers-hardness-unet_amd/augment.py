@@ -122,6 +122,7 @@ class DeviceDataset:
         self.masks = torch.empty(n, S, S, dtype=torch.uint8, device=self.device)
         lib, st = L.lib(), L.current_stream()
         keep = []
+        self.content = np.zeros((n, 4), np.int32)            # (top, left, nh, nw): where each item's pixels lie in its square
         for i, (im, mk) in enumerate(zip(images_bgr, masks)):
             im = np.ascontiguousarray(im)
             mk = np.ascontiguousarray(mk[:, :, 0] if mk.ndim == 3 else mk)           # train.py:163-164
@@ -129,6 +130,7 @@ class DeviceDataset:
                 raise ValueError(f"item {i}: expected uint8 BGR [h, w, 3] and uint8 mask [h, w]")
             h, w = im.shape[:2]
             _, nh, nw, top, left = letterbox_geometry(h, w, S, "train")
+            self.content[i] = (top, left, nh, nw)
             ti, tm = torch.from_numpy(im).to(self.device), torch.from_numpy(mk).to(self.device)
             keep += [ti, tm]
             d = L.vk_letterbox_desc(h, w, 3 * w, S, nh, nw, top, left, 0)

@@ -41,7 +41,7 @@ SENTINEL = 77.0                                                    # exact in ev
 WS_BYTES = 64 << 20                                                # VK_WGRAD_WORKSPACE_BYTES
 SPLITK_BYTES = 32 << 20                                            # VK_SPLITK_WORKSPACE_BYTES
 ENV_KEYS = ["VK_COL_ALT", "VK_COL_PIPE", "VK_COL_PERSIST", "VK_COL_PERSIST_GRID", "VK_STREAM_RS", "VK_NO_STREAM", "VK_COL_NO_KYFAST",
-            "VK_HALO_ROWSTAGED", "VK_NO_S2_TILE", "VK_NO_HALO", "VK_SPLITK", "VK_NO_SPLITK", "VK_IGEMM_NO_PARITY", "VK_NO_WGRAD_HALO",
+            "VK_NO_S2_TILE", "VK_NO_HALO", "VK_SPLITK", "VK_NO_SPLITK", "VK_IGEMM_NO_PARITY", "VK_NO_WGRAD_HALO",
             "VK_WH_MINBLOCKS", "VK_WH_MAXCOMBO", "VK_WGRAD_ATOMICS", "VK_WH_NO_TS", "VK_WH_BLOCKS", "VK_WS_KW", "VK_NO_WSTREAM",
             "VK_WH_NO_SLAB", "VK_NO_STEM_TILE", "VK_STEM_WGRAD_TAPS"]
 
@@ -197,14 +197,14 @@ def fwd_paths(case, dtn):
     kernels under that environment and through vk_conv_fwd with plain weights otherwise (the streaming and C = 16 kernels take plain
     weights); `igemm` is always the tap-by-tap implicit-GEMM kernel."""
     one = {"VK_COL_PERSIST": "0"}
-    paths = {"igemm": {"VK_NO_HALO": "1"}, "default": {}, "tile": one, "rowstaged": dict(one, VK_HALO_ROWSTAGED="1")}
+    paths = {"igemm": {"VK_NO_HALO": "1"}, "default": {}, "tile": one}
     if case.stride == 2:
         paths["no_s2_tile"] = {"VK_NO_S2_TILE": "1"}
         return paths
     if case.R != 3:
         return paths
     if case.K >= 128:
-        for alt in "12378":
+        for alt in "2378":
             paths[f"tile_alt{alt}"] = dict(one, VK_COL_ALT=alt)
         for alt in "27":
             paths[f"tile_alt{alt}_plain"] = dict(one, VK_COL_ALT=alt, VK_COL_PIPE="0")
@@ -318,7 +318,7 @@ def dgrad_paths(case, dtn):
     if case.R != 3:
         return paths
     if case.K >= 128:
-        for alt in "12378":
+        for alt in "2378":
             paths[f"tile_alt{alt}"] = dict(one, VK_COL_ALT=alt)
     else:
         paths["tile_persist"] = {"VK_COL_PERSIST": "2", "VK_COL_PERSIST_GRID": "3"}

@@ -100,10 +100,10 @@ def conv_run(d, w, y, y1=None, split=0, acc=0, stats=None, plain=False):
     return packed
 
 
-@pytest.fixture(params=["tile", "tile_alt1", "tile_alt2", "tile_alt3", "tile_alt7", "tile_alt8", "tile_alt2_plain", "tile_alt7_plain",
+@pytest.fixture(params=["tile", "tile_alt2", "tile_alt3", "tile_alt7", "tile_alt8", "tile_alt2_plain", "tile_alt7_plain",
                         "tile_alt2_stag", "tile_alt7_stag", "tile_persist", "tap"])
 def conv_path(request, monkeypatch):
-    """tile: 3x3 stride-1 tile kernels with halo-pack weights (alt1/2/3/7/8: each tile shape of the K >= 128 class forced; the
+    """tile: 3x3 stride-1 tile kernels with halo-pack weights (alt2/3/7/8: each tile shape of the K >= 128 class forced; the
     8-wave shapes 2 and 7 run the software-pipelined kernel by default, `_plain` = their plain stage loop, VK_COL_PIPE=0,
     `_stag` = the staggered form conv3x3_cols_kernel, VK_COL_PIPE=2);
     tile_persist: the persistent form of the K < 128 tile kernels forced onto the small test shapes, THREE workgroups walking all

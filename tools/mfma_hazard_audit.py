@@ -7,8 +7,8 @@ front of a wave-uniform branch (`if (want_sums)`), and the block at the branch t
 MFMA's result: on the TAKEN edge (no statistics pointer) only 2 wait states separate the two, the hazard recogniser's `s_nop`
 sits behind that first read (it covers the following three reads, which have exactly the 8 states it gives every other row), and
 the read returns the accumulator's previous contents — element 3 of every lane's 4-channel group, in every output row of that loop
-phase.  tests/diag/stream_race_diag.py shows exactly that footprint (rows y = 3 mod 4, channels 19, 23, 27, 31), and
-tests/diag/vmcnt_order_probe.hip shows that vmcnt retires in issue order (stores never overtake older loads).
+phase.  A rebuild of that code showed exactly that footprint (rows y = 3 mod 4, channels 19, 23, 27, 31;
+profiles/r04/stream_race_r03.log), and tests/diag/vmcnt_order_probe.hip shows that vmcnt retires in issue order (stores never overtake older loads).
 
 What is checked: for every MFMA, along every path of the function's control-flow graph (conditional branches: both edges), the
 number of wait states (instructions issued; `s_nop N` = N + 1) up to the first NON-MFMA instruction that names a register of

@@ -7,12 +7,17 @@
 //   * per 64-byte channel chunk (32 x 16-bit or 16 x fp32 channels) the (TH+2) x 18 halo is staged ONCE
 //     (BatchNorm scale/shift + ReLU, nearest-x2 upsample and channel concat applied on the way) and feeds
 //     all 9 taps: 9x less gather traffic / prologue VALU / LDS writes than tap-by-tap implicit GEMM.
-//   * weights stream through LDS one filter row (3 taps) at a time, double buffered; the next chunk's
-//     halo and the next row's weights are prefetched into registers underneath the MFMAs; one barrier per
-//     filter row (48-96 MFMAs per wave between barriers).
-//   * LDS image: 64-byte rows, 16-byte chunk j of row r stored at j ^ (((r >> 2) & 1) << 1): conflict-free
-//     ds_read_b128 for 16 consecutive rows at ANY row offset (tap shifts), no padding.
+//   * a pipeline stage is (channel chunk, filter COLUMN): the weights of its three taps go from the halo pack
+//     (vk_halo_pack: the LDS image itself) into LDS by LDS-DMA, one stage or more ahead; the next chunk's
+//     halo is prefetched into registers underneath the MFMAs (conv3x3_col_kernel and the forms after it).
+//   * halo image: 96-byte pixel stride (64 B + 32 B pad); weight image: 64-byte rows, 16-byte piece j of row r
+//     stored at j ^ (((r >> 2) & 1) << 1): conflict-free ds_read_b128 at any tap shift.
 //   * 16x16 MFMA tiles, "swapped" orientation, epilogue through LDS with BN partial sums — as conv_igemm.
+// The kernels: conv3x3_col_kernel (plain stage loop: K < 128, short reductions, stride 2), conv3x3_colq_kernel
+// (software-pipelined, the 8-wave K >= 128 tiles; conv3x3_cols_kernel: its staggered form, opt-in, measured slower),
+// conv3x3_colp_kernel (persistent, K < 128), conv3x3_s2dg_kernel
+// (stride-2 data gradient), conv3x3_c16_kernel and conv3x3_stream_kernel (C = 16 / 32 decoder layers), stem7x7_kernel,
+// dec4_tail_eval_kernel.  col_select and conv3x3_halo_try at the end of the file choose among them.
 #include <stdlib.h>
 #include <string.h>
 
@@ -29,22 +34,6 @@
 
 namespace vk {
 
-// -DVK_COLQ_PRE=0: the pipelined K >= 128 kernel's epilogue requests the accumulate / BN-backward operands pass by pass (r03 form)
-#ifndef VK_EPI_BATCH_READS
-#define VK_EPI_BATCH_READS 1    // plain-store epilogue: the tile rows of up to 8 passes are read from LDS up front (0: one read -> wait -> store per pass, r03)
-#endif
-#ifndef VK_COLP_DEFER_STATS
-#define VK_COLP_DEFER_STATS 1   // persistent K < 128 kernel: BN sums accumulate across a workgroup's tiles, one atomic pair at the end (0: per tile, r03)
-#endif
-#ifndef VK_COLQ_ILV
-#define VK_COLQ_ILV 1           // weight DMAs of a stage issued between the MFMAs of filter row 2 (0: in front of them, r03)
-#endif
-#ifndef VK_COLQ_DIAG
-#define VK_COLQ_DIAG 0          // knock-out timing builds of the pipelined K >= 128 loop (WRONG results): 1 one weight DMA per wave and stage, 2 no halo store, 4 no halo loads
-#endif
-#ifndef VK_COLQ_PRE
-#define VK_COLQ_PRE 1
-#endif
 struct HaloParams {
   Src s0, s1;
   const void* w;
@@ -63,43 +52,11 @@ struct HaloParams {
   int ksplit;                   // > 1: blockIdx.z owns a slice of the channel chunks and writes an fp32 partial tile into `slab`
   size_t slab_bytes;
   float* slab;                  //      [ksplit][N*H*W][K]; k_splitk_reduce adds the slices up in a fixed order (small grids: batch-1 inference)
-  int dbg;                      // timing experiments (VK_COL_DBG, results are WRONG by construction): 1 = weight descriptor with zero
-                                // records, 2 = no LDS-DMA in the loop, 4 = no halo refresh in the loop, 8 = no stage barriers
   const void* bnr_z;
   const float* bnr_scale;
   const float* bnr_shift;
   double* bnr_sums;
   const void* bnr_mask;         // != nullptr: ReLU mask = [bnr_mask > 0] (a residual block's stored output) instead of the affine of bnr_z
-};
-
-template <typename T, int TH, int BN, int WGM, int WGN>
-struct HaloCfg {
-  using Tr = ElemTraits<T>;
-  static constexpr int EB = Tr::kBytes;
-  static constexpr int VE = Tr::kVec;
-  static constexpr int CK = 64 / EB;                 // channels per chunk
-  static constexpr int HW_ = 18, HH = TH + 2, HPIX = HH * HW_;
-  static constexpr int APS = 96;                     // halo pixel stride: 64 B + 32 B pad => conflict-free at any shift, addresses = base + immediate
-  static constexpr int A_BYTES = HPIX * APS;         // single buffer (next chunk's halo waits in registers)
-  static constexpr int B_BYTES = 3 * BN * 64;        // one filter row of weights, XOR-swizzled 64-B rows, double buffered
-  static constexpr int NPV = (HPIX * 4 + 255) / 256;   // halo vectors per thread
-  static constexpr int NBV = (3 * BN * 4 + 255) / 256; // weight vectors per thread per filter row
-  static constexpr int BM = TH * 16;
-  static constexpr int WR = TH / WGM;                  // tile rows per wave (= MFMA pixel tiles)
-  static constexpr int WCH = BN / WGN;
-  static constexpr int TP = WR, TC = WCH / 16;
-  static constexpr int ESB = BN * EB + 16;
-  static constexpr int EVPR = BN / VE;
-  static constexpr int ERPP = 256 / EVPR;
-  static constexpr int EPASS = BM / ERPP;
-  static constexpr int RED_OFF = BM * ESB;
-  static constexpr int MAIN = A_BYTES + 2 * B_BYTES;
-  static constexpr int ESLOTS = (BN / VE > 16) ? 4 * 4 / (BN / VE / 16) : 4 * 4;
-  static constexpr int EPI = RED_OFF + ESLOTS * BN * 2 * 4;       // + [wave x 16-lane row][channel][2] partial sums
-  static constexpr int SMEM = MAIN > EPI ? MAIN : EPI;
-  static_assert(WGM * WGN == 4 && TH % WGM == 0 && BN % (16 * WGN) == 0, "wave layout");
-  static_assert(EPASS >= 1, "epilogue mapping");
-  static_assert(SMEM <= 160 * 1024, "main-loop / epilogue LDS image exceeds the 160 KiB of a CU");
 };
 
 __device__ __forceinline__ int swz(int row) { return ((row >> 2) & 1) << 1; }
@@ -280,10 +237,10 @@ __device__ __forceinline__ void halo_epilogue(char* smem, f32x4_t (&acc)[TC][TP]
   } else {
     // plain store: the LDS tile already holds the rounded values, so they go out as they are (no pack / unpack round trip) and only
     // a launch that wants BN statistics pays for the sums.  r04: the tile rows of up to 8 passes are read from LDS up front (in
-    // bounds for every thread) instead of one dependent ds_read -> wait -> store chain per pass behind the bounds branch
-    // (VK_EPI_BATCH_READS=0: the r03 order); the operand vectors of the path above are dead here, so this costs no registers.
+    // bounds for every thread) instead of one dependent ds_read -> wait -> store chain per pass behind the bounds branch;
+    // the operand vectors of the path above are dead here, so this costs no registers.
     // Measured null on layers 1-2 (profiles/r04/epi_batch_ab.log): the other workgroup of the CU hides the chain
-    constexpr int RB = VK_EPI_BATCH_READS ? (EPASS < 8 ? EPASS : 8) : 1;
+    constexpr int RB = EPASS < 8 ? EPASS : 8;
     u32x4_t raws[RB];
 #pragma unroll
     for (int ps = 0; ps < EPASS; ++ps) {
@@ -383,231 +340,10 @@ __device__ __forceinline__ void stats_flush(const HaloParams& p, int n0, double 
   d[1] = 0.0;
 }
 
-template <typename T, int TH, int BN, int WGM, int WGN>
-__global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(const HaloParams p) {
-  using Cfg = HaloCfg<T, TH, BN, WGM, WGN>;
-  constexpr int EB = Cfg::EB, VE = Cfg::VE, CK = Cfg::CK, HPIX = Cfg::HPIX, NPV = Cfg::NPV, NBV = Cfg::NBV;
-  constexpr int TP = Cfg::TP, TC = Cfg::TC, APS = Cfg::APS;
-
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* const Abuf = smem;
-  char* const Bbuf = smem + Cfg::A_BYTES;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-
-  // block -> (image, tile y, tile x), channel tile
-  int bt = blockIdx.x;
-  // workgroups go round-robin over the 8 XCDs: give every XCD (its own L2) a contiguous run of tiles so that horizontally
-  // adjacent tiles share their halo columns in one L2 (kernel level +1-2 % on the HBM-bound layers, null on the step)
-  if ((gridDim.x & 7) == 0) bt = (bt & 7) * (int)(gridDim.x >> 3) + (bt >> 3);
-  const int tx = bt % p.tiles_x;
-  bt /= p.tiles_x;
-  const int ty = bt % p.tiles_y;
-  const int n = bt / p.tiles_y;
-  const int y0 = ty * TH, x0 = tx * 16;
-  const int n0 = blockIdx.y * BN;
-
-  const __amdgpu_buffer_rsrc_t rs0 = make_rsrc(p.s0.ptr, p.s0.bytes);
-  const __amdgpu_buffer_rsrc_t rs1 = make_rsrc(p.s1.ptr ? p.s1.ptr : p.s0.ptr, p.s1.ptr ? p.s1.bytes : 0u);
-  const __amdgpu_buffer_rsrc_t rsw = make_rsrc(p.w, p.w_bytes);
-
-  // ---- per-thread staging geometry, computed once (the main loop only adds block-uniform scalars)
-  const int hv = tid & 3;                       // 16-byte vector inside the 64-byte pixel chunk (fixed per thread)
-  const int hgrp = halo_group(tid);
-  int h_full[NPV], h_half[NPV];                 // pixel index in a full-res / half-res (upsampled) source, -1 = outside
-  const int Hh = p.H >> 1, Wh = p.W >> 1;
-#pragma unroll
-  for (int i = 0; i < NPV; ++i) {
-    const int hp = hgrp + i * 64;
-    const int hy = hp / 18, hx = hp - hy * 18;
-    const int y = y0 - 1 + hy, x = x0 - 1 + hx;
-    const bool ok = hp < HPIX && (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W;
-    h_full[i] = ok ? (n * p.H + y) * p.W + x : -1;
-    h_half[i] = ok ? (n * Hh + (y >> 1)) * Wh + (x >> 1) : -1;
-  }
-  // weights come in the "halo pack": [chunk][tap][K rows][64 B], the 16-byte pieces of a row already XOR-swizzled the way
-  // the LDS image wants them.  A stage (chunk, filter row) = three contiguous BN x 64-byte slabs -> every wave-instruction
-  // copies 1 KiB of consecutive bytes (the stamp profile showed the former [K][tap][C] gather costing as much as the MFMAs).
-  // Data-gradient mode walks the taps backwards (tap 8 - t) instead of flipping the halo accesses.
-  int b_toff[NBV];                               // byte offset of this thread's vector inside its slab, -1 = unused slot
-  int b_s[NBV];                                  // which of the three taps of the stage
-#pragma unroll
-  for (int i = 0; i < NBV; ++i) {
-    const int idx = tid + i * 256;
-    b_s[i] = idx / (BN * 4);
-    b_toff[i] = idx < 3 * BN * 4 ? (idx - b_s[i] * (BN * 4)) * 16 : -1;
-  }
-  const uint32_t slab_bytes = (uint32_t)p.K * 64u;         // one (chunk, tap) slab
-
-  u32x4_t areg[NPV], breg0[NBV], breg1[NBV];   // weights are prefetched TWO filter rows ahead (two register sets)
-  float sc[VE], sh[VE];
-  bool aff = false, relu = false;
-
-  auto load_halo = [&](int cc) {
-    const int c = cc * CK;
-    const bool first = c < p.s0.C;
-    const Src& sd = first ? p.s0 : p.s1;
-    const int cl = (first ? c : c - p.s0.C) + hv * VE;
-    aff = sd.scale != nullptr;
-    relu = sd.relu != 0;
-    if (aff) {
-#pragma unroll
-      for (int j = 0; j < VE; j += 4) {
-        const f32x4_t s4 = *reinterpret_cast<const f32x4_t*>(sd.scale + cl + j);
-        const f32x4_t h4 = *reinterpret_cast<const f32x4_t*>(sd.shift + cl + j);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { sc[j + e] = s4[e]; sh[j + e] = h4[e]; }
-      }
-    }
-    const bool up = sd.up != 0;
-#pragma unroll
-    for (int i = 0; i < NPV; ++i) {
-      const int pix = up ? h_half[i] : h_full[i];
-      const uint32_t off = (uint32_t)(pix * sd.C + cl) * (uint32_t)EB;
-      if (first) areg[i] = buf_load16(rs0, pix >= 0 ? off : kOOB);
-      else areg[i] = buf_load16(rs1, pix >= 0 ? off : kOOB);
-    }
-  };
-
-  auto store_halo = [&]() {
-#pragma unroll
-    for (int i = 0; i < NPV; ++i) {
-      const int hp = hgrp + i * 64;
-      if (hp >= HPIX) continue;
-      u32x4_t v = areg[i];
-      if (aff) {
-        v = AffineRelu<T>::run(v, sc, sh, relu);
-        if (h_full[i] < 0) v = u32x4_t{0, 0, 0, 0};     // zero padding is applied after BN+ReLU
-      }
-      *reinterpret_cast<u32x4_t*>(Abuf + hp * APS + hv * 16) = v;
-    }
-  };
-
-  // weights of filter row r, chunk cc: rows n0..n0+BN, three taps
-  auto load_b = [&](u32x4_t (&breg)[NBV], int stage) {
-    const int cc = stage / 3, r = stage - cc * 3;
-#pragma unroll
-    for (int i = 0; i < NBV; ++i) {
-      const int tap = p.flip ? 8 - (3 * r + b_s[i]) : 3 * r + b_s[i];
-      const uint32_t base = (uint32_t)(cc * 9 + tap) * slab_bytes + (uint32_t)n0 * 64u;     // block-uniform per tap
-      breg[i] = buf_load16(rsw, b_toff[i] >= 0 ? base + (uint32_t)b_toff[i] : kOOB);
-    }
-  };
-  auto store_b = [&](const u32x4_t (&breg)[NBV], int buf) {
-    char* B = Bbuf + buf * Cfg::B_BYTES;
-#pragma unroll
-    for (int i = 0; i < NBV; ++i)
-      if (b_toff[i] >= 0) *reinterpret_cast<u32x4_t*>(B + b_s[i] * (BN * 64) + b_toff[i]) = breg[i];     // linear copy
-  };
-
-  // ---- accumulators and per-lane fragment bases (fragment reads are base + immediate)
-  const int wrow0 = (wave / WGN) * Cfg::WR;
-  const int wch0 = (wave % WGN) * Cfg::WCH;
-  f32x4_t acc[TC][TP];
-#pragma unroll
-  for (int a = 0; a < TC; ++a)
-#pragma unroll
-    for (int b = 0; b < TP; ++b) acc[a][b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-  const int li = lane & 15, kg = lane >> 4;
-  const char* const a_lane = Abuf + (wrow0 * 18 + li) * APS + kg * 16;
-  const int b_lane = (wch0 + li) * 64 + ((kg ^ swz(li)) << 4);       // swz(row) only depends on li: rows step by 16
-
-  auto compute = [&](int bbuf, int r) {
-    const char* A = a_lane + r * (18 * APS);
-    const char* B = Bbuf + bbuf * Cfg::B_BYTES + b_lane;
-    // fragments of tap s+1 are read before the MFMAs of tap s are issued (explicit one-tap software pipeline)
-    u32x4_t wf[2][TC], xf[2][TP];
-#pragma unroll
-    for (int a = 0; a < TC; ++a) wf[0][a] = *reinterpret_cast<const u32x4_t*>(B + (a * 16) * 64);
-#pragma unroll
-    for (int b = 0; b < TP; ++b) xf[0][b] = *reinterpret_cast<const u32x4_t*>(A + (b * 18) * APS);
-#pragma unroll
-    for (int s = 0; s < 3; ++s) {
-      if (s < 2) {
-#pragma unroll
-        for (int a = 0; a < TC; ++a) wf[(s + 1) & 1][a] = *reinterpret_cast<const u32x4_t*>(B + ((s + 1) * BN + a * 16) * 64);
-#pragma unroll
-        for (int b = 0; b < TP; ++b) xf[(s + 1) & 1][b] = *reinterpret_cast<const u32x4_t*>(A + (b * 18 + s + 1) * APS);
-      }
-#pragma unroll
-      for (int a = 0; a < TC; ++a)
-#pragma unroll
-        for (int b = 0; b < TP; ++b) acc[a][b] = Mma<T>::run(wf[s & 1][a], xf[s & 1][b], acc[a][b]);
-    }
-    // pin the issue order: [reads tap0][reads tap1][MFMAs tap0][reads tap2][MFMAs tap1][MFMAs tap2]
-    constexpr int NR = TC + TP, NM = TC * TP * (sizeof(T) == 4 ? 4 : 1);
-    __builtin_amdgcn_sched_group_barrier(0x100, NR, 0);
-    __builtin_amdgcn_sched_group_barrier(0x100, NR, 0);
-    __builtin_amdgcn_sched_group_barrier(0x008, NM, 0);
-    __builtin_amdgcn_sched_group_barrier(0x100, NR, 0);
-    __builtin_amdgcn_sched_group_barrier(0x008, NM, 0);
-    __builtin_amdgcn_sched_group_barrier(0x008, NM, 0);
-  };
-
-#ifdef VK_STAMP
-  unsigned long long t_begin;
-  VK_T(t_begin)
-#endif
-  // ---- pipeline over (chunk, filter row) stages.  Halo: single LDS buffer, next chunk waits in registers for three
-  // stages.  Weights: two LDS buffers + two register sets, i.e. the global loads of stage s+2 are issued before the
-  // MFMAs of stage s and written to LDS after the MFMAs of stage s+1 (a full stage of slack for the L2/HBM latency).
-  const int nst = p.nchunks * 3;
-  load_halo(0);
-  load_b(breg0, 0);
-  store_halo();
-  store_b(breg0, 0);
-  if (nst > 1) load_b(breg1, 1);
-  __syncthreads();
-
-#ifdef VK_STAMP
-  unsigned long long tk_load = 0, tk_comp = 0, tk_store = 0, tk_bar = 0;
-#endif
-  auto stage = [&](int st, u32x4_t (&ld_regs)[NBV], const u32x4_t (&st_regs)[NBV]) {
-    const int cc = st / 3, r = st - cc * 3;
-    const bool next_chunk = cc + 1 < p.nchunks;
-#ifdef VK_STAMP
-    unsigned long long t0, t1, t2, t3, t4;
-#endif
-    VK_T(t0)
-    if (st + 2 < nst) load_b(ld_regs, st + 2);
-    if (r == 0 && next_chunk) load_halo(cc + 1);
-    VK_T(t1)
-    compute(st & 1, r);
-    VK_T(t2)
-    if (r == 2 && next_chunk) {
-      __syncthreads();                                  // every wave is done reading this chunk's halo
-      store_halo();
-    }
-    if (st + 1 < nst) store_b(st_regs, (st + 1) & 1);
-    VK_T(t3)
-    __syncthreads();
-    VK_T(t4)
-#ifdef VK_STAMP
-    tk_load += t1 - t0; tk_comp += t2 - t1; tk_store += t3 - t2; tk_bar += t4 - t3;
-#endif
-  };
-  for (int st = 0; st < nst; st += 2) {
-    stage(st, breg0, breg1);                            // even stage: reads B[0], stores set 1 -> B[1], loads set 0
-    if (st + 1 < nst) stage(st + 1, breg1, breg0);      // odd stage : reads B[1], stores set 0 -> B[0], loads set 1
-  }
-
-#ifdef VK_STAMP
-  unsigned long long te0, te1;
-  VK_T(te0)
-#endif
-  halo_epilogue<T, TH, BN, TP, TC>(smem, acc, p, n, y0, x0, n0, wrow0, wch0);
-#ifdef VK_STAMP
-  VK_T(te1)
-  if (p.stamps && lane == 0) {
-    unsigned long long* o = p.stamps + ((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 4 + wave) * 8;
-    o[0] = tk_load; o[1] = tk_comp; o[2] = tk_store; o[3] = tk_bar; o[4] = te1 - te0; o[5] = te0 - t_begin; o[6] = te1 - t_begin; o[7] = nst;
-  }
-#endif
-}
-
-// ---- column-staged variant (v2 main loop).  Same tile / halo / epilogue as above, different dataflow:
+// ---- the column-staged main loop:
 //   * a stage is (channel chunk, filter COLUMN s): the wave reads its TP+2 halo rows once at column shift s and uses each of them
 //     for up to three filter rows (row h feeds output rows h, h-1, h-2) -> (TP + 2 + 3 TC) fragment reads per 3 TP TC MFMAs
-//     instead of 3 (TP + TC): 0.375 reads per MFMA at TP = TC = 4, 0.23 at TP = 8 (the row-staged loop sits at 0.5 and is
+//     instead of 3 (TP + TC): 0.375 reads per MFMA at TP = TC = 4, 0.23 at TP = 8 (a loop staged by filter ROW sits at 0.5 and is
 //     LDS-bound: LDS reads + ds_write_b128 of the weights come to ~90 % of the LDS cycles at full MFMA rate).
 //   * weights never touch a VGPR: the halo pack is the LDS image, so a stage's three taps are 3 BN / 16 linear 1-KiB pieces
 //     copied by LDS-DMA (buffer_load_dwordx4 ... lds), issued one stage ahead into the other weight buffer and retired by
@@ -699,7 +435,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, MINW) void conv3x3_col_kernel(const
   const __amdgpu_buffer_rsrc_t rs1 = make_rsrc(p.s1.ptr ? p.s1.ptr : p.s0.ptr, p.s1.ptr ? p.s1.bytes : 0u);
   const __amdgpu_buffer_rsrc_t rsw = make_rsrc(p.w, p.w_bytes);
 
-  // ---- halo staging geometry (as in the row-staged kernel, NT threads)
+  // ---- halo staging geometry, computed once (the main loop only adds block-uniform scalars)
   const int hv = tid & 3;
   const int hgrp = halo_group(tid);
   int h_full[NPV], h_half[NPV];
@@ -823,7 +559,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, MINW) void conv3x3_col_kernel(const
   const int c_begin = (int)((long)p.nchunks * blockIdx.z / ksp), c_end = (int)((long)p.nchunks * (blockIdx.z + 1) / ksp);
   load_halo(c_begin);
   dma_b(c_begin, 0, 0);
-  const bool one_chunk = Cfg::NB == 3 && c_end - c_begin == 1 && !p.dbg;
+  const bool one_chunk = Cfg::NB == 3 && c_end - c_begin == 1;
   if (one_chunk) {                                        // all three filter columns now: the stages need no barrier between them
     dma_b(c_begin, 1, 1);
     dma_b(c_begin, 2, 2);
@@ -851,24 +587,22 @@ __global__ __launch_bounds__(64 * WGM * WGN, MINW) void conv3x3_col_kernel(const
 #endif
       VK_T(t0)
       // next stage's weights into the other buffer (all waves passed the barrier that closed its last readers)
-      if (!(p.dbg & 2)) {
-        if (s < 2) dma_b(cc, s + 1, (st + 1) & 1);
-        else if (next_chunk) dma_b(cc + 1, 0, (st + 1) & 1);
-      }
-      if (s == 0 && next_chunk && !(p.dbg & 4)) load_halo(cc + 1);
+      if (s < 2) dma_b(cc, s + 1, (st + 1) & 1);
+      else if (next_chunk) dma_b(cc + 1, 0, (st + 1) & 1);
+      if (s == 0 && next_chunk) load_halo(cc + 1);
       VK_T(t1)
       compute(A + (STR == 1 ? s : (s & 1) * 17 + (s >> 1)) * APS, Bbuf + (st & 1) * Cfg::B_BYTES + b_lane);
       VK_T(t2)
       if (ADB) {
-        if (s == 1 && next_chunk && !(p.dbg & 4)) store_halo(Anext);
+        if (s == 1 && next_chunk) store_halo(Anext);
       } else {
-        if (s == 2 && next_chunk && !(p.dbg & 4)) {
+        if (s == 2 && next_chunk) {
           __syncthreads();                                // every wave is done reading this chunk's halo
           store_halo(Anext);
         }
       }
       VK_T(t3)
-      if (!(p.dbg & 8)) __syncthreads();
+      __syncthreads();
       VK_T(t4)
 #ifdef VK_STAMP
       tk_load += t1 - t0; tk_comp += t2 - t1; tk_store += t3 - t2; tk_bar += t4 - t3;
@@ -1177,7 +911,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, 1) void conv3x3_colq_kernel(const H
       if (hp >= HPIX) continue;
       u32x4_t v = areg[i];
       if (aff) {
-        v = (p.dbg & 32) ? AffineReluScalar<T>::run(v, sc, sh, relu) : AffineRelu<T>::run(v, sc, sh, relu);
+        v = AffineRelu<T>::run(v, sc, sh, relu);
         if (h_full[i] < 0) v = u32x4_t{0, 0, 0, 0};
       }
       *reinterpret_cast<u32x4_t*>(A + hp * APS + hv * 16) = v;
@@ -1187,26 +921,18 @@ __global__ __launch_bounds__(64 * WGM * WGN, 1) void conv3x3_colq_kernel(const H
   // weights of stage (chunk cc, filter column s) -> weight buffer s
   const uint32_t slab_bytes = (uint32_t)p.K * 64u;
   const uint32_t lane16 = (uint32_t)lane * 16u;
-  auto dma_b = [&](int cc, int s, uint32_t oob = 0u) {       // oob = kOOB: issued, but out of the descriptor's range (fetches nothing; keeps the vmcnt pattern uniform)
-#pragma unroll
-    for (int i = 0; i < ((VK_COLQ_DIAG & 1) ? 1 : Cfg::DMAW); ++i) {      // diagnostic bit 1: one piece per wave and stage (timing only)
-      const int pc = wave + i * NW;
-      const int r = pc / (BN / 16), sub = pc - r * (BN / 16);
-      const int tap = p.flip ? 8 - (3 * r + s) : 3 * r + s;
-      const uint32_t goff = (uint32_t)(cc * 9 + tap) * slab_bytes + (uint32_t)(n0 + sub * 16) * 64u;
-      char* dst = Bbuf + s * Cfg::B_BYTES + (r * BN + sub * 16) * 64;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (lds_void*)dst, 16, lane16 | oob, goff, 0, 0);     // (the VECTOR offset is the range-checked one)
-    }
-  };
-
-
+  // piece i of this wave; oob = kOOB: issued, but out of the descriptor's range (fetches nothing; keeps the vmcnt pattern uniform)
   auto dma_one = [&](int cc, int s, int i, uint32_t oob) {
     const int pc = wave + i * NW;
     const int r = pc / (BN / 16), sub = pc - r * (BN / 16);
     const int tap = p.flip ? 8 - (3 * r + s) : 3 * r + s;
     const uint32_t goff = (uint32_t)(cc * 9 + tap) * slab_bytes + (uint32_t)(n0 + sub * 16) * 64u;
     char* dst = Bbuf + s * Cfg::B_BYTES + (r * BN + sub * 16) * 64;
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (lds_void*)dst, 16, lane16 | oob, goff, 0, 0);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (lds_void*)dst, 16, lane16 | oob, goff, 0, 0);     // (the VECTOR offset is the range-checked one)
+  };
+  auto dma_b = [&](int cc, int s) {
+#pragma unroll
+    for (int i = 0; i < Cfg::DMAW; ++i) dma_one(cc, s, i, 0u);
   };
 
   const int wrow0 = (wave / WGN) * TP;
@@ -1283,47 +1009,34 @@ __global__ __launch_bounds__(64 * WGM * WGN, 1) void conv3x3_colq_kernel(const H
       __builtin_amdgcn_sched_group_barrier(0x008, NM, 0);
       __builtin_amdgcn_sched_group_barrier(0x100, 1 + TC + TP / 2, 0);
       __builtin_amdgcn_sched_group_barrier(0x008, NM, 0);
-      if (s == 1 && next_chunk && !(VK_COLQ_DIAG & 2)) store_halo(Anext);          // diagnostic bit 2: no operand transform / halo store in the loop
+      if (s == 1 && next_chunk) store_halo(Anext);
       // every wave: its reads of this stage's weights / halo rows have returned, its halo stores are in LDS, and of its vector
       // memory operations only the DMAW youngest (the weights of stage st + 2) may still be in flight
       asm volatile("" ::: "memory");
-      if (VK_COLQ_ILV) __builtin_amdgcn_s_waitcnt(kWaitPart);     // the last chunk issues its (out-of-range) DMAs too
-      else if (next_chunk) __builtin_amdgcn_s_waitcnt((VK_COLQ_DIAG & 1) ? ((1 & 0xF) | 0x70) : kWaitPart);
-      else __builtin_amdgcn_s_waitcnt(kWaitAll);
+      __builtin_amdgcn_s_waitcnt(kWaitPart);                      // the last chunk issues its (out-of-range) DMAs too
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-      if (VK_COLQ_ILV) {
-        // r04: the weight DMAs of the stage are issued BETWEEN the MFMAs of filter row 2, not in front of them: all eight
-        // waves leave the barrier together and queue 24 vector-memory instructions at the CU's address unit while no MFMA is in
-        // flight (knock-out builds: 16 of them cost 12-15 % of the kernel).  Needs one basic block: the DMAs are issued in the last
-        // chunk as well, out of the descriptor's range
-        if (s == 0 && next_chunk && !(VK_COLQ_DIAG & 4)) load_halo(cc + 1);
+      // -- filter row 2; under it: the next stage's filter row 0 (its weights became visible with the barrier) and the LDS-DMA of
+      // stage st + 3 into the buffer every wave has just finished reading.
+      // r04: those weight DMAs are issued BETWEEN the MFMAs of filter row 2, not in front of them: all eight waves leave the barrier
+      // together and queue 24 vector-memory instructions at the CU's address unit while no MFMA is in flight (knock-out builds: 16
+      // of them cost 12-15 % of the kernel).  Needs one basic block: the DMAs are issued in the last chunk as well, out of the
+      // descriptor's range.  The halo loads go in front of them: the DMAs stay the youngest vector-memory operations
+      if (s == 0 && next_chunk) load_halo(cc + 1);
 #pragma unroll
-        for (int a = 0; a < TC; ++a) W0n[a] = rd(Bn + (a * 16) * 64);
-        const uint32_t oob = next_chunk ? 0u : kOOB;
-        constexpr int NT2 = TC * TP, GRP = NT2 / (Cfg::DMAW + 1);
+      for (int a = 0; a < TC; ++a) W0n[a] = rd(Bn + (a * 16) * 64);
+      const uint32_t oob = next_chunk ? 0u : kOOB;
+      constexpr int NT2 = TC * TP, GRP = NT2 / (Cfg::DMAW + 1);
 #pragma unroll
-        for (int i = 0; i <= Cfg::DMAW; ++i) {
-          const int lo = i * GRP, hi = i == Cfg::DMAW ? NT2 : (i + 1) * GRP;
+      for (int i = 0; i <= Cfg::DMAW; ++i) {
+        const int lo = i * GRP, hi = i == Cfg::DMAW ? NT2 : (i + 1) * GRP;
 #pragma unroll
-          for (int q = lo; q < hi; ++q) acc[q / TP][q % TP] = Mma<T>::run(W2[q / TP], X[q % TP + 2], acc[q / TP][q % TP]);
-          if (i < Cfg::DMAW) {
-            __builtin_amdgcn_sched_barrier(0);
-            dma_one(cc + 1, s, i, oob);
-            __builtin_amdgcn_sched_barrier(0);
-          }
+        for (int q = lo; q < hi; ++q) acc[q / TP][q % TP] = Mma<T>::run(W2[q / TP], X[q % TP + 2], acc[q / TP][q % TP]);
+        if (i < Cfg::DMAW) {
+          __builtin_amdgcn_sched_barrier(0);
+          dma_one(cc + 1, s, i, oob);
+          __builtin_amdgcn_sched_barrier(0);
         }
-      } else {
-      if (next_chunk) {
-        if (s == 0 && !(VK_COLQ_DIAG & 4)) load_halo(cc + 1);   // in front of the DMAs: those stay the youngest operations (diagnostic bit 4: no halo loads)
-        dma_b(cc + 1, s);                                   // stage st + 3 -> the buffer every wave has just finished reading
-      }
-      // -- filter row 2; under it: the next stage's filter row 0 (its weights became visible with the barrier)
-      if (more) {
-#pragma unroll
-        for (int a = 0; a < TC; ++a) W0n[a] = rd(Bn + (a * 16) * 64);
-      }
-      mfma_row(W2, 2);
       }
       if (more) {
 #pragma unroll
@@ -1333,7 +1046,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, 1) void conv3x3_colq_kernel(const H
       }
     }
   }
-  if (VK_COLQ_ILV) __builtin_amdgcn_s_waitcnt(kWaitAll);    // the last chunk's out-of-range DMAs have retired
+  __builtin_amdgcn_s_waitcnt(kWaitAll);                     // the last chunk's out-of-range DMAs have retired
   __syncthreads();                                          // every wave is done with the operand buffers: the epilogue reuses them
 
   if (p.ksplit > 1) {
@@ -1347,7 +1060,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, 1) void conv3x3_colq_kernel(const H
       }
     return;
   }
-  halo_epilogue<T, TH, BN, TP, TC, NT, ((VK_COLQ_PRE && sizeof(T) == 2) || (BN <= 64 && TH == 16))>(smem, acc, p, n, y0, x0, n0, wrow0, wch0);
+  halo_epilogue<T, TH, BN, TP, TC, NT, (sizeof(T) == 2 || (BN <= 64 && TH == 16))>(smem, acc, p, n, y0, x0, n0, wrow0, wch0);
 }
 
 // ---- staggered form of the pipelined kernel (r03): the same tile, operand order and epilogue (bit-identical results), but the two
@@ -1572,10 +1285,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, 1) void conv3x3_cols_kernel(const H
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
       VK_T(t3)
-      // ---- slot Y: the first fragments of the next stage are requested FIRST (their latency runs under the halo / DMA work below);
-      // p.dbg & 16 (timing experiment, results unchanged): this slot at raised priority, so that its few vector instructions are
-      // not queued behind the partner wave's MFMA stream
-      if (p.dbg & 16) __builtin_amdgcn_s_setprio(1);
+      // ---- slot Y: the first fragments of the next stage are requested FIRST (their latency runs under the halo / DMA work below)
       if (more) {
 #pragma unroll
         for (int h = 0; h < TP; ++h) X[h] = rd(An + h * (18 * APS));
@@ -1590,7 +1300,6 @@ __global__ __launch_bounds__(64 * WGM * WGN, 1) void conv3x3_cols_kernel(const H
       }
       asm volatile("" ::: "memory");
       __builtin_amdgcn_s_waitcnt(kWaitLds);                 // fragment reads returned, halo stores in LDS
-      if (p.dbg & 16) __builtin_amdgcn_s_setprio(0);
       VK_T(t4)
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
@@ -1829,7 +1538,8 @@ __global__ __launch_bounds__(64 * WGM * WGN, MINW) void conv3x3_colp_kernel(cons
     stage(p.nchunks - 1, I1{}, std::true_type{});
     stage(p.nchunks - 1, I2{}, std::true_type{});
     // aff / relu / sc / sh now describe the prefetched chunk (chunk 0 of the next tile): exactly what its store_halo needs
-    constexpr bool DEFER = VK_COLP_DEFER_STATS && (sizeof(T) == 2 || BN < 64);       // (the fp32 64-channel tile has no two registers left)
+    // BN sums accumulate across a workgroup's tiles, one atomic pair at the end (the fp32 64-channel tile has no two registers left)
+    constexpr bool DEFER = sizeof(T) == 2 || BN < 64;
     halo_epilogue<T, TH, BN, TP, TC, NT, (BN <= 64 && TH == 16)>(smem, acc, p, g.n, g.y0, g.x0, g.n0, wrow0, wch0, 0, 0, DEFER ? dsum : nullptr);
     if (DEFER && (!more_tiles || gn.n0 != g.n0)) stats_flush<BN>(p, g.n0, dsum);
     if (!more_tiles) break;
@@ -2104,9 +1814,6 @@ __global__ __launch_bounds__(256) void conv3x3_c16_kernel(const HaloParams p) {
 // C = 32 the tile kernels add (filter column, filter row) instead: results differ in fp32 rounding order (a last-bit flip of the
 // stored value on < 5 % of the elements, tests/test_ops_gpu.py::test_stream_conv_kernels_match_tile_kernels).  Statistics are over the
 // stored (rounded) values, pooling adds the four rounded values in the tile kernels' order.
-#ifndef VK_STREAM_DIAG
-#define VK_STREAM_DIAG 0      // diagnostic builds only (tests/diag/stream_race_diag.py)
-#endif
 template <typename T, int CIN, bool UP>
 struct StreamCfg {
   static constexpr int NSTEP = CIN == 16 ? 5 : 9;
@@ -2222,9 +1929,6 @@ __global__ __launch_bounds__(256) void conv3x3_stream_kernel(const HaloParams p)
   auto write_row = [&](int j, const u32x4_t (&r)[NLD]) {
     const bool rok = (unsigned)j < (unsigned)Hs;
     char* const slot = ring + (j & 3) * ROWB;
-#if (VK_STREAM_DIAG & 1)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
 #pragma unroll
     for (int q = 0; q < NLD; ++q) {
       if (st_off[q] < 0) continue;
@@ -2235,9 +1939,6 @@ __global__ __launch_bounds__(256) void conv3x3_stream_kernel(const HaloParams p)
       }
       *reinterpret_cast<u32x4_t*>(slot + st_off[q]) = v;
     }
-#if (VK_STREAM_DIAG & 2)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
   };
 
   // ---- fragment-read geometry: step -> (filter row r, column s); C = 16: per lane (two taps per step), C = 32: per step
@@ -2284,9 +1985,6 @@ __global__ __launch_bounds__(256) void conv3x3_stream_kernel(const HaloParams p)
   const int Ho = POOL ? Hh : p.H, Wo = POOL ? Wh : p.W;
   const uint32_t out_bytes = (uint32_t)((size_t)p.N * Ho * Wo * ld * 2);
   const __amdgpu_buffer_rsrc_t rsbz = make_rsrc(BNR ? p.bnr_z : p.y0, out_bytes);
-#ifdef VK_STREAM_BUFSTORE
-  const __amdgpu_buffer_rsrc_t rsy = make_rsrc(p.y0, out_bytes);
-#endif
   const bool lane_stores = x_ok && (!POOL || (li & 1) == 0);
   const uint32_t lane_ob = lane_stores ? (uint32_t)(((n * Ho) * Wo + (POOL ? (xo >> 1) : xo)) * ld + kg * 4) * 2u : kOOB;
   const uint32_t row_ob = (uint32_t)(Wo * ld * 2);
@@ -2323,18 +2021,8 @@ __global__ __launch_bounds__(256) void conv3x3_stream_kernel(const HaloParams p)
     // a plain (global) store under a lane predicate.  (r03 blamed MUBUF stores for the wrong 16-bit inference of 04e3d09..75808a4;
     // r04 found the cause elsewhere — an MFMA-result read 2 wait states behind its MFMA across a branch, see the sched_barrier in
     // row() — and tests/diag/vmcnt_order_probe.hip shows stores never leave the vmcnt queue ahead of older loads on this chip:
-    // 0 of 2.1 M wave-probes.  VK_STREAM_BUFSTORE rebuilds the MUBUF form for tests/diag/stream_race_diag.py.)
-#ifdef VK_STREAM_BUFSTORE      // diagnostic build only (r03 bug reconstruction, tests/diag/README.md): the MUBUF store form
-#if (VK_STREAM_DIAG & 8)
-    if ((int32_t)boff >= 0)
-#endif
-    __builtin_amdgcn_raw_buffer_store_b64(pk, rsy, boff, 0, 0);
-#if (VK_STREAM_DIAG & 4)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-#else
+    // 0 of 2.1 M wave-probes.)
     if ((int32_t)boff >= 0) *reinterpret_cast<u32x2_t*>((char*)p.y0 + boff) = pk;
-#endif
   };
 
   // ---- the row pipeline.  Source row j lives in queue register set j & 3 until it is written to ring slot j & 3; the loop is
@@ -2395,9 +2083,7 @@ __global__ __launch_bounds__(256) void conv3x3_stream_kernel(const HaloParams p)
     // hazard recogniser pads everywhere else: element 3 of every lane's channel group came out stale in every fourth output row.
     // With the barrier the last MFMA is followed by straight-line code (padded correctly); tools/mfma_hazard_audit.py checks the
     // shipped binary for this pattern along every control-flow path (tests/test_host_cpu.py).
-#if !(VK_STREAM_DIAG & 16)      // 16: the r03 code without the barrier (diagnostic builds only)
     __builtin_amdgcn_sched_barrier(0);
-#endif
     const bool y_ok = y < p.H;
 #pragma unroll
     for (int a = 0; a < TC; ++a) {
@@ -2694,20 +2380,6 @@ int halo_pack_impl(vk_dtype dt, int rows, int red, const void* src, void* dst, h
 // ------------------------------------------------------------------------------------------------ host
 static vkh::ProfDetail hkc_detail(const HaloParams& p) { return {":H%d_K%d_C%d", {p.H, p.K, p.C}}; }
 
-template <typename T, int TH, int BN, int WGM, int WGN>
-static int launch_halo(HaloParams p, hipStream_t st) {
-  using Cfg = HaloCfg<T, TH, BN, WGM, WGN>;
-  p.tiles_x = (p.W + 15) / 16;
-  p.tiles_y = (p.H + TH - 1) / TH;
-  dim3 grid((unsigned)(p.N * p.tiles_y * p.tiles_x), (unsigned)((p.K + BN - 1) / BN), 1);
-  static const std::string tag_f = std::string("halo_") + (sizeof(T) == 4 ? "f32" : "16b") + "_t" + std::to_string(TH) + "_bn" + std::to_string(BN);
-  static const std::string tag_d = tag_f + "_dgrad";
-  const double macs = (double)p.N * p.H * p.W * p.K * 9.0 * p.C;
-  const double bytes = ((double)p.N * p.H * p.W * (p.C + p.K) + 9.0 * p.K * p.C) * sizeof(T);
-  return vkh::launch<conv3x3_halo_kernel<T, TH, BN, WGM, WGN>>(grid, dim3(256), Cfg::SMEM, st, (p.flip ? tag_d : tag_f).c_str(), hkc_detail(p), 2.0 * macs,
-                                                               bytes, p);
-}
-
 // y[e] = T(sum_s slab[s][e]) in slice order (reproducible), four elements per thread
 template <typename T>
 __global__ __launch_bounds__(256) void k_splitk_reduce(size_t n4, int splits, const float* __restrict__ slab, T* __restrict__ y) {
@@ -2825,9 +2497,8 @@ static int launch_small(const HaloParams& p, hipStream_t st) {
   return launch_col<T, 16, BN, 4, 1, false, 2>(p, st);
 }
 
-// tile selection for the column-staged kernels.  VK_COL_ALT (diagnostic / tests) forces a shape of the K >= 128 class:
-//   1: 4 waves, 16x16x128, 8 rows x 64 channels per wave (one wave per SIMD);  2: the 8-wave 16x16x128 tile;  3: the 4-wave 8x16x128 tile;
-//   7: the 8-wave 8x16x128 tile;  8: the 4-wave 16x16x64 tile
+// tile selection for the column-staged kernels.  VK_COL_ALT (tests: the default-route kernels at small shapes) forces a shape of the
+// K >= 128 class:  2: the 8-wave 16x16x128 tile;  3: the 4-wave 8x16x128 tile;  7: the 8-wave 8x16x128 tile;  8: the 4-wave 16x16x64 tile
 template <typename T>
 static int col_select(const HaloParams& p, hipStream_t st) {
   const char* alt_s = getenv("VK_COL_ALT");
@@ -2835,7 +2506,6 @@ static int col_select(const HaloParams& p, hipStream_t st) {
   const long tiles16 = (long)p.N * ((p.H + 15) / 16) * ((p.W + 15) / 16);
   if (p.K >= 128) {
     const long kt = (p.K + 127) / 128;
-    if (alt == 1) return launch_col<T, 16, 128, 2, 2, true, 1>(p, st);
     // a short reduction onto a channel count that is not a multiple of 128 (the concat gradient of decoder block 2: 64 -> 192):
     // 64-channel tiles waste no half-empty channel tile (201 -> 156 us stand-alone)
     // ... and a ONE-chunk reduction onto 128+ channels (the concat gradient of decoder block 3: 32 -> 128) as well: the 64-channel
@@ -2853,9 +2523,6 @@ static int col_select(const HaloParams& p, hipStream_t st) {
     if (alt == 7 || (alt != 2 && tiles16 * kt < 256))
       return pipe == 2 ? launch_col<T, 8, 128, 2, 4, true, 1, 2>(p, st)
              : pipe    ? launch_col<T, 8, 128, 2, 4, true, 1, 1>(p, st) : launch_col<T, 8, 128, 2, 4, true, 2>(p, st);
-    // experiment (VK_COL_ALT=9): 8 rows x 32 channels per wave — 16 instead of 18 fragment reads per stage and wave (the K >= 128 loop asks
-    // 75 % of the LDS read bandwidth at the full MFMA rate: DESIGN.md section 6)
-    if (alt == 9) return launch_col<T, 16, 128, 2, 4, true, 1, 1>(p, st);
     return pipe == 2 ? launch_col<T, 16, 128, 4, 2, true, 1, 2>(p, st)       // 8 waves, 4 rows x 64 channels per wave
            : pipe    ? launch_col<T, 16, 128, 4, 2, true, 1, 1>(p, st) : launch_col<T, 16, 128, 4, 2, true, 2>(p, st);
   }
@@ -2864,24 +2531,6 @@ static int col_select(const HaloParams& p, hipStream_t st) {
   // byte): dec3.conv1 forward 265 -> 255 us, dec4.conv1 244 -> 243 us, dec3.conv2 data gradient + reduce 109 -> 131 us
   if (p.K >= 32) return launch_small<T, 32>(p, st);
   return launch_small<T, 16>(p, st);
-}
-
-template <typename T>
-static int halo_select(const HaloParams& p, hipStream_t st) {
-  const bool old_loop = getenv("VK_HALO_ROWSTAGED") != nullptr;             // diagnostic: the v1 row-staged main loop
-  if (!old_loop) return col_select<T>(p, st);
-  const long tiles8 = (long)p.N * ((p.H + 7) / 8) * ((p.W + 15) / 16);
-  const long tiles16 = (long)p.N * ((p.H + 15) / 16) * ((p.W + 15) / 16);
-  if (p.K >= 128) {
-    if (tiles8 * ((p.K + 127) / 128) >= 512) return launch_halo<T, 8, 128, 2, 2>(p, st);
-    return launch_halo<T, 8, 64, 2, 2>(p, st);
-  }
-  if (p.K >= 64) {
-    if (tiles16 >= 1024) return launch_halo<T, 16, 64, 4, 1>(p, st);
-    return launch_halo<T, 8, 64, 2, 2>(p, st);
-  }
-  if (p.K >= 32) return launch_halo<T, 16, 32, 4, 1>(p, st);
-  return launch_halo<T, 16, 16, 4, 1>(p, st);
 }
 
 template <typename T, int BN>
@@ -2934,8 +2583,7 @@ static int launch_stream(const HaloParams& p, hipStream_t st) {
 }
 
 // the streaming kernel is instantiated for the launches of decoder blocks 3 / 4 that it is faster on (one source, K in one part, no
-// accumulate); everything else stays on the tile kernels.  VK_NO_STREAM=1 (tests / A-B): tile kernels only;
-// VK_STREAM_ALL=1: every instantiated combination, also where the tile kernels measured faster
+// accumulate); everything else stays on the tile kernels.  VK_NO_STREAM=1 (tests / A-B): tile kernels only
 template <typename T>
 static int stream_try(const HaloParams& p, hipStream_t st) {
   if (getenv("VK_NO_STREAM")) return VK_ERR_UNSUPPORTED;
@@ -3007,8 +2655,6 @@ int conv3x3_halo_try(const vk_conv_desc* d, const void* w, int packed, void* y, 
   p.slab = (reinterpret_cast<uintptr_t>(workspace) & 15) ? nullptr : (float*)workspace;      // 16-byte stores into the slab
   p.slab_bytes = p.slab ? workspace_bytes : 0;
   p.stamps = nullptr;
-  p.dbg = getenv("VK_COL_DBG") ? atoi(getenv("VK_COL_DBG")) : 0;
-  if (p.dbg & 1) p.w_bytes = 0;
 #ifdef VK_STAMP
   { extern unsigned long long* g_vk_stamp_buf; p.stamps = g_vk_stamp_buf; }
 #endif
@@ -3040,7 +2686,7 @@ int conv3x3_halo_try(const vk_conv_desc* d, const void* w, int packed, void* y, 
     p.slab_bytes = 0;
     return dispatch_dtype(d->dtype, [&](auto e) { return launch_col<decltype(e), 8, 128, 2, 4, false, 1, 0, 2>(p, st); });
   }
-  return dispatch_dtype(d->dtype, [&](auto e) { return halo_select<decltype(e)>(p, st); });
+  return dispatch_dtype(d->dtype, [&](auto e) { return col_select<decltype(e)>(p, st); });
 }
 
 }  // namespace vk

@@ -19,21 +19,10 @@
 
 #include "conv_host.h"
 
-// -DVK_WH_PIPE=1: the fragment reads of the 2x2-wave 16-bit tiles software-pipelined two (step, tap) units ahead (compute_tile_pipe) —
-// built, bit-identical, 174 tests green, and measured 2-3 % SLOWER than the per-step form in same-box A/B runs through VK_LIB
-// (profiles/r03/wgrad_pipe_experiment.log: 64x64 tap-split kernel 1.839 -> 1.902 ms per step): the partner wave already covers the
-// LDS latency the compiler's schedule exposes; what bounds this kernel is the LDS pipe itself (1.2 transposed reads per MFMA + the
-// staging writes: ~87 % of its cycles).  Default 0 = the per-step form.  Compile-time: both forms in one kernel cost 48 registers.
-#ifndef VK_WH_PIPE
-#define VK_WH_PIPE 0
-#endif
-// -DVK_WH_ZDMA=0: dz of the 64 x 64 tap-split configuration staged through registers + ds_write_b128 as in r03 (A/B builds through VK_LIB)
-#ifndef VK_WH_XCD
-#define VK_WH_XCD 1
-#endif
-#ifndef VK_WH_ZDMA
-#define VK_WH_ZDMA 1
-#endif
+// Measured and rejected (r03): the fragment reads of the 2x2-wave 16-bit tiles software-pipelined two (step, tap) units ahead —
+// bit-identical and 2-3 % SLOWER than the per-step form (profiles/r03/wgrad_pipe_experiment.log: 64x64 tap-split kernel 1.839 ->
+// 1.902 ms per step): the partner wave already covers the LDS latency the compiler's schedule exposes; what bounds this kernel is the
+// LDS pipe itself (1.2 transposed reads per MFMA + the staging writes: ~87 % of its cycles).
 
 namespace vk {
 
@@ -45,7 +34,7 @@ struct WhParams {
   int N, H, W, K, C;            // H, W: size of dz (= of the input for the stride-1 layers)
   int Hi, Wi;                   // size of the input V (stride 2: 2 H x 2 W)
   int tiles_x, tiles_y, ntiles, splits;
-  int dbg_skip_epilogue;      // timing experiments only (VK_WH_DBG_NOEPI)
+  int dbg_skip_epilogue;      // always 0 (make_wh_params; no switch sets it any more) — see the tile loop of wh_segment for why it is still there
   float* slab;                // [splits][K][9][C] partial results (deterministic two-stage reduce) or nullptr (atomics)
 };
 
@@ -69,7 +58,7 @@ struct WhCfg {
   // 128-byte pixel rows whose 32-byte slots are XOR-swizzled with (row >> 1) & 3 — the swizzle sits in the per-lane SOURCE address
   // (the DMA writes 1 KiB = 8 rows x 8 pieces linearly) and in the transposed fragment reads, which stay conflict-free: the eight
   // pixel rows one 32-lane group of a ds_read_b64_tr_b16 touches land in eight different 32-byte slots of the 256-byte bank row.
-  static constexpr bool ZDMA = VK_WH_ZDMA && TS && !WS && EB == 2 && STR == 1 && KT == 64;
+  static constexpr bool ZDMA = TS && !WS && EB == 2 && STR == 1 && KT == 64;
   static constexpr int ZSB = ZDMA ? KT * EB : KT * EB + zpad(KT);
   static constexpr int VSB = CT * EB + zpad(CT);
   static constexpr int STAGE = PX * ZSB + HHI * HRS * VSB;
@@ -110,7 +99,6 @@ __device__ __forceinline__ void wh_segment(const WhParams& p, char* smem, const 
   const bool affine = sd.scale != nullptr;
   const bool relu = sd.relu != 0;
   constexpr bool ZDMA = Cfg::ZDMA;
-  static_assert(!(ZDMA && VK_WH_PIPE), "the pipelined fragment reads do not know the swizzled dz image");
   typedef __attribute__((address_space(3))) void lds_void;
 
   // this thread's V vectors always cover the same channels -> scale/shift once
@@ -334,69 +322,17 @@ __device__ __forceinline__ void wh_segment(const WhParams& p, char* smem, const 
     }
   };
 
-  // ---- the same four 32-pixel steps as ONE software pipeline over (step, tap) units (16-bit, 2x2 wave layout, stride 1):
-  // the transposed fragment reads of unit u + 2 are issued in front of the MFMAs of unit u, so every read has two units (8 MFMAs,
-  // >= 128 matrix cycles) to return — the per-step form leaves the compiler to place them, and it waits lgkmcnt(1..3) one or two
-  // MFMAs after issuing them (ISA of r02: the LDS latency shows at every tap).  Three V fragment sets, two dz fragment sets;
-  // same accumulation order per accumulator (steps 0..3), so the results are bit-identical.
-  auto compute_tile_pipe = [&](const char* Zs, const char* Vs, auto hsel_c) {
-    constexpr int HSEL = decltype(hsel_c)::value;
-    constexpr int TAP0 = HSEL == 2 ? 5 : 0;
-    constexpr int NTP = HSEL == 0 ? 9 : (HSEL == 1 ? 5 : 4);
-    constexpr int U = 4 * NTP;
-    const char* const Zl = Zs + lane_z;
-    const char* const Vl = Vs + lane_v;
-    u32x4_t zf[2][TK], vf[3][TCc];
-    auto tr = [](const char* q) {
-      const s16x4_t v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(q));
-      return __builtin_bit_cast(u32x2_t, v);
-    };
-    auto load_unit = [&](auto u_c) {
-      constexpr int u = decltype(u_c)::value;
-      constexpr int ks = u / NTP, tap = TAP0 + u % NTP, r = tap / 3, sx = tap % 3;
-      if constexpr (u % NTP == 0) {
-#pragma unroll
-        for (int a = 0; a < TK; ++a) {
-          const char* b0 = Zl + (32 * ks) * ZSB + (a * 16) * 2;
-          const u32x2_t lo = tr(b0), hi = tr(b0 + 16 * ZSB);
-          zf[ks & 1][a] = u32x4_t{lo[0], lo[1], hi[0], hi[1]};
-        }
-      }
-#pragma unroll
-      for (int b = 0; b < TCc; ++b) {
-        const char* b0 = Vl + ((2 * ks + r) * 18 + sx) * VSB + (b * 16) * 2;
-        const u32x2_t lo = tr(b0), hi = tr(b0 + HRS * VSB);
-        vf[u % 3][b] = u32x4_t{lo[0], lo[1], hi[0], hi[1]};
-      }
-    };
-    auto mma_unit = [&](auto u_c) {
-      constexpr int u = decltype(u_c)::value;
-      constexpr int ks = u / NTP, t = u % NTP;
-#pragma unroll
-      for (int a = 0; a < TK; ++a)
-#pragma unroll
-        for (int b = 0; b < TCc; ++b) acc[t][a][b] = Mma<T>::run(zf[ks & 1][a], vf[u % 3][b], acc[t][a][b]);
-    };
-    auto unit = [&](auto u_c, auto&& self) {
-      constexpr int u = decltype(u_c)::value;
-      if constexpr (u < U) {
-        if constexpr (u + 2 < U) {
-          load_unit(std::integral_constant<int, u + 2>{});
-          __builtin_amdgcn_sched_group_barrier(0x100, ((u + 2) % NTP == 0 ? 2 * TK : 0) + 2 * TCc, 0);
-        }
-        mma_unit(u_c);
-        __builtin_amdgcn_sched_group_barrier(0x008, TK * TCc, 0);
-        self(std::integral_constant<int, u + 1>{}, self);
-      }
-    };
-    load_unit(std::integral_constant<int, 0>{});
-    load_unit(std::integral_constant<int, 1>{});
-    __builtin_amdgcn_sched_group_barrier(0x100, 2 * TK + 4 * TCc, 0);
-    unit(std::integral_constant<int, 0>{}, unit);
-  };
-
   // ---- stream over this workgroup's pixel tiles: t = blockIdx.z, + splits, ...
-  const int dbg = p.dbg_skip_epilogue >> 1;     // timing experiments (VK_WH_DBG, results WRONG): 1 no tile loads, 2 no LDS tile stores, 4 no MFMA steps, 8 no barriers
+  // `dbg` is always 0: the host sets the field to 0 and reads no switch for it.  Its tests below are what is left of the r02-r04
+  // knock-out timing switches (1 no tile loads, 2 no LDS tile stores, 4 no MFMA steps, 8 no barriers), and they stay because hipcc's
+  // register allocation hangs on one of them: with the MFMA steps unconditional (no test of bit 4) the AGPR count of the WS tiles
+  // doubles — 144 -> 256 in the 32 x 32 tiles (VGPRs 152 -> 256; fp32: 716 bytes of scratch), 72 -> 144 and 36 -> 72 in the smaller
+  // ones, 28 bytes of scratch in the stride-2 tile (profiles/retired/README.md section 2); that it keeps a second copy of the
+  // accumulators is inferred from those counts, not read from its passes.  The other three tests and the one in front of the
+  // epilogue do not affect the allocation; they stay so that this code is instruction for instruction what was measured.
+  // Follow-up: replace all of it by something that is not a field — an opaque zero (`asm volatile("" : "+s"(z))`) or a scheduling
+  // fence around the MFMA steps — drop the field and the five tests, and measure the fp32, fp16 and stride-2 tiles one by one.
+  const int dbg = p.dbg_skip_epilogue >> 1;
   int t = t0;
   if (t < t_end) {
     load_tile(t, zreg[0], vreg[0], vmask[0]);
@@ -427,15 +363,11 @@ __device__ __forceinline__ void wh_segment(const WhParams& p, char* smem, const 
         } else {
           // the next tile's LDS writes (other stage buffer) go between the 32-pixel steps instead of after the last one: the
           // ds_write_b128 transfers then run beside the MFMAs of the remaining steps instead of in front of the barrier
-          if constexpr (VK_WH_PIPE && EB == 2 && STR == 1) {
-            compute_tile_pipe(Zs, Vs, hsel_c);
-          } else {
-            compute_step(Zs, Vs, 0, hsel_c);
-            compute_step(Zs, Vs, 1, hsel_c);
-            if (STORE_MID && more && !(dbg & 2)) { store_tile((it + 1) & 1, zs, vs, ms); stored = true; }
-            compute_step(Zs, Vs, 2, hsel_c);
-            compute_step(Zs, Vs, 3, hsel_c);
-          }
+          compute_step(Zs, Vs, 0, hsel_c);
+          compute_step(Zs, Vs, 1, hsel_c);
+          if (STORE_MID && more && !(dbg & 2)) { store_tile((it + 1) & 1, zs, vs, ms); stored = true; }
+          compute_step(Zs, Vs, 2, hsel_c);
+          compute_step(Zs, Vs, 3, hsel_c);
         }
       }
       if (!stored && more && !(dbg & 2)) store_tile((it + 1) & 1, zs, vs, ms);
@@ -536,9 +468,9 @@ __global__ __launch_bounds__(512) void wgrad_halo_batch_kernel(const WhParams* _
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // workgroups go round-robin over the 8 XCDs (each with its own L2): XCD x takes the x-th eighth of the unit list, so that the
   // workgroups walking neighbouring output tiles of a layer — which read the same dz tiles (same K tile) or the same operand tiles
-  // (same C tile) at about the same time — share one L2 (VK_WH_XCD=0: workgroup b takes range b, r03)
+  // (same C tile) at about the same time — share one L2
   int b = (int)blockIdx.x;
-  if (VK_WH_XCD && (gridDim.x & 7) == 0) b = (b & 7) * (int)(gridDim.x >> 3) + (b >> 3);
+  if ((gridDim.x & 7) == 0) b = (b & 7) * (int)(gridDim.x >> 3) + (b >> 3);
   const int s0 = wg_first[b], s1 = wg_first[b + 1];
   for (int s_ = s0; s_ < s1; ++s_) {
     const WhSeg sg = segs[s_];
@@ -638,11 +570,8 @@ struct WsArgs {
   int RS, c_dst0, nks;
 };
 
-#ifndef VK_WS_MINWG
-#define VK_WS_MINWG 2
-#endif
 template <typename T, int K, bool UP>
-__global__ __launch_bounds__(256, (K == 16 ? (UP ? VK_WS_MINWG : 2) : 1)) void wgrad_stream_kernel(const WhParams p, const WsArgs wa) {
+__global__ __launch_bounds__(256, (K == 16 ? 2 : 1)) void wgrad_stream_kernel(const WhParams p, const WsArgs wa) {
   using Cfg = WsCfg<T, K, UP>;
   const int RS = wa.RS;
   const int chunk = (int)blockIdx.y / wa.nks, kslice = (int)blockIdx.y - chunk * wa.nks;
@@ -915,7 +844,6 @@ static int launch_wh(WhParams p, size_t slab_bytes, hipStream_t st) {
   if (splits < 1) splits = 1;
   if ((long)splits * kt * ct < wh_min_blocks()) return VK_ERR_UNSUPPORTED;  // too few workgroups to fill the chip
   p.splits = splits;
-  p.dbg_skip_epilogue = (getenv("VK_WH_DBG_NOEPI") ? 1 : 0) | ((getenv("VK_WH_DBG") ? atoi(getenv("VK_WH_DBG")) : 0) << 1);
   const size_t slab_need = (size_t)splits * p.K * 9 * p.C * sizeof(float);
   if (!p.slab || slab_need > slab_bytes || getenv("VK_WH_NO_SLAB")) p.slab = nullptr;
   dim3 grid(kt, ct, splits);
@@ -973,7 +901,7 @@ static int launch_ws(WhParams p, int c_dst0, char* slab, size_t slab_bytes, size
   const long per_image = (long)((p.W + 15) / 16);
   // exactly ONE round of resident waves (measured: D3c2 73 / 93 / 134 us at 1 / 2 / 4 rounds, D4c1 132 / 105 / 118 us at 0.5 / 1 / 2):
   // 36 accumulator tiles run one wave per SIMD (1024 waves), 18 tiles two (2048)
-  const long want = KW == 32 ? 1024 : 1024 * (UP ? VK_WS_MINWG : 2);
+  const long want = KW == 32 ? 1024 : 2048;
   const long want_e = getenv("VK_WS_WANT") ? atol(getenv("VK_WS_WANT")) : 0;
   while (RS > 32 && (long)p.N * per_image * ((p.H + RS - 1) / RS) * gy < (want_e ? want_e : want)) RS >>= 1;
   RS = (RS + 1) & ~1;

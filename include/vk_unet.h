@@ -42,6 +42,7 @@
  *                                               reference trains on letterboxed images only)
  *   vk_cp_boxes / vk_cp_alpha / vk_cp_paste ... instance copy-paste between the letterboxed items (no counterpart: the reference never
  *                                               composes images)
+ *   vk_edt_sq / vk_boundary_phi / _stats / _loss  distance maps, surface-distance metrics and the boundary loss (no counterpart)
  *
  * Conventions
  *   - plain pointers and sizes only; no C++/torch types cross this boundary.
@@ -559,6 +560,77 @@ int vk_cp_alpha(int batch, int h, int w, const int32_t* slots, uint8_t* kept, ui
 int vk_cp_paste(int n, int S, int n_items, const uint8_t* images_rgb, const uint8_t* masks, const uint8_t* kept, const uint8_t* alpha,
                 const int32_t* base_index_dev, const int32_t* counts_host, const vk_cp_rec* recs_host, void* recs_dev, uint8_t* out_rgb,
                 uint8_t* out_mask, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Distance maps of masks: the exact squared Euclidean distance transform, the signed map of the boundary loss
+ * (Kervadec et al., MIDL 2019), surface-distance statistics of a prediction against its label, and the boundary loss.  Distances are
+ * integers: the results are the numbers a numpy restatement gives again (tests/boundary_ref.py).
+ *
+ * vk_edt_sq: src [batch][h][w], uint8 (foreground: != 0) or fp32 (foreground: v > thresh; thresh is ignored for uint8) ->
+ * d2 int32 [batch][h][w] = min over the site pixels (y', x') of the same image of (y - y')^2 + (x - x')^2; 0 on a site; VK_EDT_NONE
+ * everywhere in an image without a site.  Sites: VK_EDT_FG the foreground, VK_EDT_BG the background, VK_EDT_EDGE the inner boundary:
+ * foreground pixels with at least one of their four neighbours inside the image in the background (beyond the border counts as
+ * foreground, so a mask that fills the image has no boundary).  1 <= h, w <= VK_EDT_MAX_SIDE, so a true value is at most
+ * 2 * 4095^2 < 2^25.  Two passes: columns (workspace int32 [batch][h][w]: the squared distance inside the column, 2^30 where the
+ * column holds no site), then rows from LDS with one wave per row: an outward search per pixel that stops at dx^2 >= best where
+ * the column distances of the row promise short walks, else the lower envelope of parabolas; sites | VK_EDT_ROWS_SEARCH or
+ * sites | VK_EDT_ROWS_ENVELOPE forces one form for every row.  Both are exact and give the same map.
+ * workspace: vk_edt_workspace_bytes (0 for sizes the call refuses), 4-byte aligned, as are d2 and an fp32 src.
+ *
+ * vk_boundary_phi: phi fp32 [batch][h][w] from the two maps of one mask: (float)sqrt((double)d2_fg) on a background pixel
+ * (d2_fg > 0), (float)(1.0 - sqrt((double)d2_bg)) on a foreground pixel, 0 where the needed map says VK_EDT_NONE (an empty or a full
+ * image is 0 everywhere).  The fp64 square root is correctly rounded: phi equals numpy's float64 sqrt cast to float32.
+ *
+ * vk_boundary_stats: one vk_boundary_rec per image from pred and gt (each with its own kind and threshold, as vk_edt_sq).  With
+ * E(.) the inner boundary and d2(p, S) the squared distance of pixel p to the set S: n_* = |E(.)|, area_* the foreground counts,
+ * max2_pg = max over E(pred) of d2(p, E(gt)), q95_2_pg its k-th smallest value, k = (95 n_pred + 99) / 100 (nearest rank: not numpy's
+ * interpolated percentile), sum_pg = sum of sqrt(d2) in fp64, within_pg[k] = |{p in E(pred): d2 <= tol2[k]}| for k < n_tol (0 beyond);
+ * *_gp the same from E(gt) to E(pred).  max2, q95_2 are -1 and the sums 0 when either boundary is empty.  band_inter / band_union:
+ * of the sets {q in A : d2(q, background of A) <= band2}, A = pred and gt (Boundary IoU, Cheng et al., CVPR 2021).  flags: bit 0
+ * pred holds no foreground, bit 1 gt holds none.  tol2 is a host array of n_tol <= 8 non-negative integers: a radius tau is
+ * floor(tau^2), since d <= tau iff d^2 <= floor(tau^2) for an integer d^2.  Integer atomics only; the fp64 sums are per-workgroup
+ * partials added in a fixed order, so two calls give the same bits.  out: device, 8-byte aligned, every byte written.  workspace:
+ * vk_boundary_stats_workspace_bytes, 8-byte aligned.
+ *
+ * vk_boundary_loss: loss_out[0] = (1 / count) sum of sigmoid(logits) phi over logits, phi fp32 [n][c][hw], count = n c hw,
+ * 1 <= c <= 16, with the sigmoid expression of vk_seg_loss; products and sums in fp64 (per-workgroup partials, fixed order), one
+ * rounding to fp32.  dlogits (may be NULL) = (float)(((phi p (1 - p)) grad_scale) / count), the bracket in fp64.  workspace:
+ * VK_BOUNDARY_LOSS_WS_BYTES, 8-byte aligned.  There is no softmax mode.
+ *
+ * Every call checks its arguments on the host (VK_ERR_ARG before anything touches the stream): batch 1..65535, the map size, the
+ * kinds, sites, no null buffer, alignment, workspace size, n_tol, negative tol2 / band2, c, a NaN threshold.
+ * ---------------------------------------------------------------------------------------------- */
+#define VK_EDT_MAX_SIDE 4096
+#define VK_EDT_NONE 0x7fffffff
+#define VK_EDT_FG 0
+#define VK_EDT_BG 1
+#define VK_EDT_EDGE 2
+#define VK_EDT_ROWS_ENVELOPE 0x100
+#define VK_EDT_ROWS_SEARCH 0x200
+#define VK_EDT_ROWS_MASK 0x300
+#define VK_EDT_SRC_U8 0
+#define VK_EDT_SRC_F32 1
+#define VK_BOUNDARY_LOSS_WS_BYTES 32768
+typedef struct vk_boundary_rec {
+  int64_t n_pred, n_gt;               /* inner-boundary pixels */
+  int64_t area_pred, area_gt;
+  int32_t max2_pg, max2_gp;           /* max d^2 from the pred boundary to the gt boundary, and back; -1 if undefined */
+  int32_t q95_2_pg, q95_2_gp;         /* k-th smallest d^2, k = (95 n + 99) / 100; -1 if undefined */
+  double sum_pg, sum_gp;              /* sum of sqrt(d^2) */
+  int64_t within_pg[8], within_gp[8]; /* boundary pixels with d^2 <= tol2[k] */
+  int64_t band_inter, band_union;
+  int32_t flags, reserved;
+} vk_boundary_rec;
+size_t vk_edt_workspace_bytes(int batch, int h, int w);
+int vk_edt_sq(int batch, int h, int w, const void* src, int src_kind, float thresh, int sites, int32_t* d2, void* workspace,
+              size_t workspace_bytes, void* stream);
+int vk_boundary_phi(int batch, int h, int w, const int32_t* d2_fg, const int32_t* d2_bg, float* phi, void* stream);
+size_t vk_boundary_stats_workspace_bytes(int batch, int h, int w);
+int vk_boundary_stats(int batch, int h, int w, const void* pred, int pred_kind, float pred_thresh, const void* gt, int gt_kind,
+                      float gt_thresh, int n_tol, const int32_t* tol2, int32_t band2, vk_boundary_rec* out, void* workspace,
+                      size_t workspace_bytes, void* stream);
+int vk_boundary_loss(int n, int c, int hw, const float* logits, const float* phi, float grad_scale, float* dlogits, float* loss_out,
+                     void* workspace, size_t workspace_bytes, void* stream);
 
 /* NCHW fp32 [N][3][H][W] -> NHWC4 `dtype` */
 int vk_input_transform(vk_dtype dtype, int N, int H, int W, const float* x, void* x4, void* stream);

@@ -98,6 +98,19 @@ def vk_cp_recs_dev_bytes(n: int) -> int:
     return n * (VK_CP_MAX_PASTES * C.sizeof(vk_cp_rec) + 4)
 
 
+VK_EDT_MAX_SIDE, VK_EDT_NONE = 4096, 0x7FFFFFFF
+VK_EDT_FG, VK_EDT_BG, VK_EDT_EDGE, VK_EDT_ROWS_ENVELOPE, VK_EDT_ROWS_SEARCH = 0, 1, 2, 0x100, 0x200
+VK_EDT_SRC_U8, VK_EDT_SRC_F32 = 0, 1
+VK_BOUNDARY_LOSS_WS_BYTES = 32768
+
+
+class vk_boundary_rec(C.Structure):
+    _fields_ = [("n_pred", C.c_int64), ("n_gt", C.c_int64), ("area_pred", C.c_int64), ("area_gt", C.c_int64), ("max2_pg", C.c_int32),
+                ("max2_gp", C.c_int32), ("q95_2_pg", C.c_int32), ("q95_2_gp", C.c_int32), ("sum_pg", C.c_double), ("sum_gp", C.c_double),
+                ("within_pg", C.c_int64 * 8), ("within_gp", C.c_int64 * 8), ("band_inter", C.c_int64), ("band_union", C.c_int64),
+                ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
 class vk_seg_loss_cfg(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("terms", C.c_uint32), ("has_ignore", C.c_int32),
                 ("ignore_index", C.c_int32), ("w_pix", C.c_float), ("w_focal", C.c_float), ("w_dice", C.c_float),
@@ -275,6 +288,12 @@ SIGNATURES = {
     "vk_cp_boxes": (ci, [ci, ci, ci, vp, ci, vp, vp]),
     "vk_cp_alpha": (ci, [ci, ci, ci, vp, vp, vp, vp]),
     "vk_cp_paste": (ci, [ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "vk_edt_workspace_bytes": (sz, [ci, ci, ci]),
+    "vk_edt_sq": (ci, [ci, ci, ci, vp, ci, cf, ci, vp, vp, sz, vp]),
+    "vk_boundary_phi": (ci, [ci, ci, ci, vp, vp, vp, vp]),
+    "vk_boundary_stats_workspace_bytes": (sz, [ci, ci, ci]),
+    "vk_boundary_stats": (ci, [ci, ci, ci, vp, ci, cf, vp, ci, cf, ci, P(C.c_int32), C.c_int32, vp, vp, sz, vp]),
+    "vk_boundary_loss": (ci, [ci, ci, ci, vp, vp, cf, vp, vp, vp, sz, vp]),
     "vk_input_transform": (ci, [ci, ci, ci, ci, vp, vp, vp]),
     "vk_bn_finalize": (ci, [ci, ci, vp, cd, vp, vp, vp, vp, cf, cf, vp, vp, vp, vp, vp]),
     "vk_bn_relu_maxpool": (ci, [ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]),

@@ -12,6 +12,7 @@
  *   vk_unet_set_trainable ..................... p.requires_grad_(False) before backward (fine-tuning with a frozen encoder)
  *   vk_unet_set_bn_frozen ..................... module.eval() of single BatchNorm layers inside a training forward
  *   vk_unet_set_input_grad .................... x.requires_grad_() (x.grad: saliency maps)
+ *   vk_unet_create_in / vk_input_mix .......... smp.Unet(in_channels=1..4) (train.py:375 passes 3) and the 3-channel data path's bridge to it
  *   vk_seg_metrics ............................ dice_coef / iou_coef (validate) train.py:230-281, 518-522
  *   vk_seg_metrics_multi ...................... the same per class for Unet(classes=C): counts tp/fp/fn/tn, Dice / IoU per class
  *   vk_sweep_hist / vk_sweep_curves ........... validate's Dice / IoU at every threshold of a grid from one pass (the reference's GUIs
@@ -204,8 +205,9 @@ int vk_conv_dgrad_fused(const vk_conv_desc* d, const void* w, void* y, void* y1,
 int vk_conv1x1_fwd(const vk_conv_desc* d, const void* w, void* y, int accumulate, double* stats, void* stream);
 int vk_conv1x1_wgrad(const vk_conv_desc* d, const void* dz, float* dw, void* workspace, size_t workspace_bytes, void* stream);
 
-/* Stem: 7x7 stride-2 pad-3 convolution of x4 [N][H][W][4] (channel 3 is zero padding) with packed
- * weights wp [64][7][32] (tap row r, 8 columns x 4 channels, zero padded). */
+/* Stem: 7x7 stride-2 pad-3 convolution of x4 [N][H][W][4] (the channels past the model's in_channels are zero padding: channel 3
+ * of the 3-channel model) with packed weights wp [64][7][32] (tap row r, 8 columns x 4 channels, zero padded).  The kernel multiplies
+ * all four channels whatever the model's count is. */
 int vk_stem_fwd(vk_dtype dtype, int N, int H, int W, const void* x4, const void* wp, void* y, double* stats,
                 void* stream);
 
@@ -236,6 +238,13 @@ int vk_stem_wgrad(vk_dtype dtype, int N, int H, int W, const void* x4, const voi
  * train.py:448 -> encoder.bn1) disappears. */
 int vk_stem_wgrad_bn(vk_dtype dtype, int N, int H, int W, const void* x4, const void* g, const void* z, const float* coef_abc,
                      float* dw_krsc3, void* workspace, size_t workspace_bytes, void* stream);
+/* The stem weight gradient for a model of cin input channels, 1 <= cin <= 4 (anything else: VK_ERR_ARG before any launch): dw is KRSC
+ * [64][7][7][cin], the columns of x4's channels >= cin are dropped in the epilogue; the partial results in `workspace` are
+ * 64 * 49 * cin floats each.  vk_stem_wgrad / vk_stem_wgrad_bn are cin = 3 of these (the same code, the same bits). */
+int vk_stem_wgrad_c(vk_dtype dtype, int N, int H, int W, int cin, const void* x4, const void* dz, float* dw_krsc, void* workspace,
+                    size_t workspace_bytes, void* stream);
+int vk_stem_wgrad_bn_c(vk_dtype dtype, int N, int H, int W, int cin, const void* x4, const void* g, const void* z, const float* coef_abc,
+                       float* dw_krsc, void* workspace, size_t workspace_bytes, void* stream);
 /* BatchNorm-backward apply + data gradient + weight gradient of one small-channel convolution in ONE pass over its tensors: 16-bit
  * types, 3x3 stride 1 pad 1, one source: up = 0 with (src0.C, K) = (16, 16) or (32, 32), or up = 1 (nearest x2) with (src0.C, K) =
  * (32, 16) and H, W even; VK_ERR_UNSUPPORTED for everything else (fp32, odd H or W and every other upsampled shape included) before any
@@ -256,6 +265,11 @@ int vk_conv_bwd_onepass(const vk_conv_desc* d_fwd, const void* g, const void* z,
  * dz = a*g + b*z + c while it loads its operand.  H % 8 == 0, W % 32 == 0. */
 int vk_stem_dgrad(vk_dtype dtype, int N, int H, int W, const void* g, const void* z, const float* coef_abc, const float* w_krsc3,
                   float* dx, void* stream);
+/* The same for cin input channels, 1 <= cin <= 4 (anything else: VK_ERR_ARG before any launch): w is KRSC [64][7][7][cin], dx fp32 NCHW
+ * [N][cin][H][W].  The 2 x 2 pixels x cin channels of an output block are columns uv * cin + c of the 16-wide tile (four channels fill
+ * it); a column's sum does not depend on where it sits.  vk_stem_dgrad is cin = 3. */
+int vk_stem_dgrad_c(vk_dtype dtype, int N, int H, int W, int cin, const void* g, const void* z, const float* coef_abc, const float* w_krsc,
+                    float* dx, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * The steps either side of model(x) in the inference wrappers, one fused pass each.
@@ -634,6 +648,16 @@ int vk_boundary_loss(int n, int c, int hw, const float* logits, const float* phi
 
 /* NCHW fp32 [N][3][H][W] -> NHWC4 `dtype` */
 int vk_input_transform(vk_dtype dtype, int N, int H, int W, const float* x, void* x4, void* stream);
+/* NCHW fp32 [N][cin][H][W] -> NHWC4 of the activation type, channels >= cin written as zero; 1 <= cin <= 4 (anything else: VK_ERR_ARG
+ * before any launch).  One 8- or 16-byte store per pixel.  vk_input_transform is cin = 3. */
+int vk_input_transform_c(vk_dtype dtype, int N, int cin, int H, int W, const float* x, void* x4, void* stream);
+/* The bridge from the device data path (which emits normalised 3-channel fp32 NCHW everywhere) to a model of cout input channels:
+ *   out[n][o][p] = fmaf(M[o][2], x2, fmaf(M[o][1], x1, fmaf(M[o][0], x0, b[o]))),   x_j = x3[n][j][p],  p < hw
+ * x3 [N][3][hw] and out [N][cout][hw] are fp32 on the device; M [cout][3] and b [cout] (NULL: zero) are HOST arrays read during the call.
+ * 1 <= cout <= 4, N <= 65535.  Each input plane is read once and each output plane written once, with 16-byte accesses where hw % 4 == 0
+ * and both tensors are 16-byte aligned (every plane then is), element accesses otherwise.  (vk.inputs.ChannelAdapter: the reference
+ * reads its monochrome micrographs with IMREAD_COLOR, i.e. replicated.) */
+int vk_input_mix(int N, int cout, size_t hw, const float* x3, const float* M, const float* b, float* out, void* stream);
 
 /* BatchNorm statistics -> per-channel affine.  train=1: from batch sums stats[VK_STATS_REPLICAS][2][C] (count = N*H*W), updates
  * running stats (momentum 0.1, unbiased var) and writes mean/invstd for backward.  train=0: from
@@ -1396,6 +1420,11 @@ int vk_unet_num_classes(const vk_unet* h);
 #define VK_ENC_RESNET50 50
 int vk_unet_create_enc(const vk_unet_config* cfg, int classes, int encoder, vk_unet** out);
 int vk_unet_encoder(const vk_unet* h);
+/* smp.Unet(in_channels=c), 1 <= c <= 4 (anything else: VK_ERR_ARG): encoder.conv1.weight is [64][c][7][7] (64 * 49 * c floats, the first
+ * tensor of the flat buffer), vk_unet_forward reads x as [N][c][H][W] and vk_unet_set_input_grad's buffer is [N][c][H][W].  The stem's
+ * kernels run on the same NHWC4 input whatever c is.  vk_unet_create_enc is in_channels = 3. */
+int vk_unet_create_in(const vk_unet_config* cfg, int classes, int encoder, int in_channels, vk_unet** out);
+int vk_unet_in_channels(const vk_unet* h);
 void vk_unet_destroy(vk_unet* h);
 /* Optional: run a training plan's weight-gradient kernels on a second, library-owned HIP stream beside the caller's stream
  * (fork per layer once dz is final, join at the end of every backward stage, before the stage's gradient bucket may be
@@ -1419,7 +1448,7 @@ int vk_unet_bind(vk_unet* h, float* params, float* grads, float* bn_buffers, int
 /* re-pack the compute copies of the weights after the fp32 master changed (load_state_dict, optimizer step) */
 int vk_unet_refresh_weights(vk_unet* h, void* stream);
 
-/* x: fp32 NCHW [N][3][S][S]; logits: fp32 [N][C][S][S] (C = classes).  training=1: batch statistics + running-stat update */
+/* x: fp32 NCHW [N][3][S][S] ([N][in_channels][S][S] for a plan of vk_unet_create_in); logits: fp32 [N][C][S][S] (C = classes).  training=1: batch statistics + running-stat update */
 int vk_unet_forward(vk_unet* h, const float* x, float* logits, int training, void* stream);
 /* target fp32 [N][1][S][S]; loss_out float[3]; computes dlogits for backward when the plan is a training plan */
 int vk_unet_loss(vk_unet* h, const float* logits, const float* target, float* loss_out, float grad_scale,
@@ -1462,7 +1491,7 @@ int vk_unet_set_trainable(vk_unet* h, const uint8_t* flags, int n);
  * forward, which normalises a frozen layer with its running statistics, leaves its running_mean / running_var /
  * num_batches_tracked untouched and records the modes for the backward that follows it.  Eval forwards (training = 0) are unchanged. */
 int vk_unet_set_bn_frozen(vk_unet* h, const uint8_t* flags, int n);
-/* Gradient of the input: dx fp32 NCHW [N][3][H][W] (or NULL: none, the default).  When set, vk_unet_backward's last stage WRITES dx
+/* Gradient of the input: dx fp32 NCHW [N][3][H][W] ([N][in_channels][H][W] for a plan of vk_unet_create_in; or NULL: none, the default).  When set, vk_unet_backward's last stage WRITES dx
  * (the input ranks behind the stem in the pruning order, so every data gradient down to the stem runs even with every parameter
  * frozen).  Host-only. */
 int vk_unet_set_input_grad(vk_unet* h, float* dx);

@@ -265,8 +265,11 @@ SIGNATURES = {
     "vk_conv_wgrad_batch": (ci, [P(vk_conv_desc), P(vp), P(vp), ci, ci, vp, sz, vp, sz, vp]),
     "vk_stem_wgrad": (ci, [ci, ci, ci, ci, vp, vp, vp, vp, sz, vp]),
     "vk_stem_wgrad_bn": (ci, [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "vk_stem_wgrad_c": (ci, [ci, ci, ci, ci, ci, vp, vp, vp, vp, sz, vp]),
+    "vk_stem_wgrad_bn_c": (ci, [ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, sz, vp]),
     "vk_conv_bwd_onepass": (ci, [P(vk_conv_desc), vp, vp, vp, vp, vp, P(vk_bnr), vp, vp, sz, vp]),
     "vk_stem_dgrad": (ci, [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]),
+    "vk_stem_dgrad_c": (ci, [ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]),
     "vk_letterbox_preprocess": (ci, [P(vk_letterbox_desc), vp, vp, vp]),
     "vk_letterbox_postprocess_mask": (ci, [P(vk_letterbox_desc), vp, cf, vp, vp]),
     "vk_letterbox_postprocess_prob": (ci, [P(vk_letterbox_desc), vp, vp, vp]),
@@ -295,6 +298,8 @@ SIGNATURES = {
     "vk_boundary_stats": (ci, [ci, ci, ci, vp, ci, cf, vp, ci, cf, ci, P(C.c_int32), C.c_int32, vp, vp, sz, vp]),
     "vk_boundary_loss": (ci, [ci, ci, ci, vp, vp, cf, vp, vp, vp, sz, vp]),
     "vk_input_transform": (ci, [ci, ci, ci, ci, vp, vp, vp]),
+    "vk_input_transform_c": (ci, [ci, ci, ci, ci, ci, vp, vp, vp]),
+    "vk_input_mix": (ci, [ci, ci, sz, vp, P(cf), P(cf), vp, vp]),
     "vk_bn_finalize": (ci, [ci, ci, vp, cd, vp, vp, vp, vp, cf, cf, vp, vp, vp, vp, vp]),
     "vk_bn_relu_maxpool": (ci, [ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]),
     "vk_maxpool_bwd": (ci, [ci, ci, ci, ci, ci, vp, vp, vp, vp]),
@@ -360,6 +365,8 @@ SIGNATURES = {
     "vk_unet_num_classes": (ci, [vp]),
     "vk_unet_create_enc": (ci, [P(vk_unet_config), ci, ci, P(vp)]),
     "vk_unet_encoder": (ci, [vp]),
+    "vk_unet_create_in": (ci, [P(vk_unet_config), ci, ci, ci, P(vp)]),
+    "vk_unet_in_channels": (ci, [vp]),
     "vk_unet_destroy": (None, [vp]),
     "vk_unet_set_side_stream": (ci, [vp, ci]),
     "vk_unet_num_tensors": (ci, [vp]),

@@ -28,7 +28,7 @@ struct WgradParams {
   float* dw;
   float* slab;            // [splits][K * RS * C] partial results (nullptr: fp32 atomics into dw)
   int N, H, W, Ho, Wo, K, R, S, slog, pad;
-  int C, M, RS, mps, ctiles, stem;
+  int C, M, RS, mps, ctiles, stem, cin;      // stem: the x4 layout; cin = its real channels (1..4), dW is [64][7][7][cin]
   FastDiv div_hw, div_w, div_ct, div_s;
 };
 
@@ -250,9 +250,9 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradParams p) {
     __syncthreads();
   }
 
-  // ---- epilogue: dW[k][tap][c] (stem: [k][r][s][3], padding columns dropped): this split's slab, or fp32 atomics ----
+  // ---- epilogue: dW[k][tap][c] (stem: [k][r][s][cin], padding columns dropped): this split's slab, or fp32 atomics ----
   // (WSPLIT layouts give every wave the whole tile on its own pixel slice: their four partial tiles are added through LDS first)
-  float* const out = p.slab ? p.slab + (size_t)blockIdx.z * ((size_t)p.K * (p.stem ? 147 : p.RS * p.C)) : p.dw;
+  float* const out = p.slab ? p.slab + (size_t)blockIdx.z * ((size_t)p.K * (p.stem ? 49 * p.cin : p.RS * p.C)) : p.dw;
   if (WSPLIT && p.slab) {
     float* red = reinterpret_cast<float*>(smem);           // [wave][TK][TCc][64 lanes][4]: at most 4 * 4 * 4 * 256 * 4 B = 64 KB <= 2 * STAGE
     static_assert(4 * TK * TCc * 1024 <= Cfg::SMEM || !WSPLIT, "wave-partial tiles must fit the staging buffers");
@@ -289,7 +289,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradParams p) {
           if (cc < p.C) dst = out + ((size_t)k * p.RS + tap) * p.C + cc;
         } else {
           const int sx = cc >> 2, ci = cc & 3;
-          if (sx < 7 && ci < 3) dst = out + (((size_t)k * 7 + tap) * 7 + sx) * 3 + ci;
+          if (sx < 7 && ci < p.cin) dst = out + (((size_t)k * 7 + tap) * 7 + sx) * p.cin + ci;
         }
         if (!dst) continue;
         if (p.slab) *dst = acc[a][b][e];
@@ -314,7 +314,7 @@ static int launch_w(WgradParams p, void* workspace, size_t workspace_bytes, hipS
   if (splits > chunks / 8) splits = chunks / 8;
   if (splits < 1) splits = 1;
   // reproducible mode: the splits' partial results go to a slab in the workspace ([splits][K * RS * C] floats) and are added in split order
-  const size_t out_elems = (size_t)p.K * (p.stem ? 147 : (size_t)p.RS * p.C);
+  const size_t out_elems = (size_t)p.K * (p.stem ? (size_t)49 * p.cin : (size_t)p.RS * p.C);
   const bool use_slab = workspace && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0 && out_elems % 4 == 0 && workspace_bytes >= out_elems * 4 &&
                         (reinterpret_cast<uintptr_t>(p.dw) & 15) == 0 && !getenv("VK_WGRAD_ATOMICS");
   if (use_slab) {
@@ -328,9 +328,9 @@ static int launch_w(WgradParams p, void* workspace, size_t workspace_bytes, hipS
   dim3 grid(ktiles, p.ctiles * p.RS, splits);
   static const std::string tag_c = std::string("wgrad_") + (sizeof(T) == 4 ? "f32" : "16b") + "_" + std::to_string(BMW) + "x" + std::to_string(BNW);
   static const std::string tag_s = std::string("wgrad_stem_") + (sizeof(T) == 4 ? "f32" : "16b");
-  const double rsc = p.stem ? 147.0 : (double)p.RS * p.C;
+  const double rsc = p.stem ? 49.0 * p.cin : (double)p.RS * p.C;
   const double eb = sizeof(T);
-  const double bytes = ((double)p.N * p.H * p.W * (p.stem ? 3 : p.C) + (double)p.M * p.K) * eb + (double)p.K * rsc * 4.0;
+  const double bytes = ((double)p.N * p.H * p.W * (p.stem ? p.cin : p.C) + (double)p.M * p.K) * eb + (double)p.K * rsc * 4.0;
   const int rc = vkh::launch<conv_wgrad_kernel<T, BMW, BNW, WSPLIT>>(grid, dim3(256), Cfg::SMEM, st, (p.stem ? tag_s : tag_c).c_str(),
                                                                      {":H%d_K%d_C%d_R%d_s%d", {p.H, p.K, p.C, p.R, splits}}, 2.0 * (double)p.M * p.K * rsc, bytes, p);
   if (rc != VK_OK || !use_slab) return rc;
@@ -381,7 +381,7 @@ int conv_wgrad_impl(const vk_conv_desc* d, const void* dz, float* dw, void* work
   p.C = C;
   p.M = d->N * d->Ho * d->Wo;
   p.RS = d->R * d->S;
-  p.stem = 0;
+  p.stem = 0; p.cin = 0;
   p.div_hw = vkh::make_fastdiv((uint32_t)(d->Ho * d->Wo));
   p.div_w = vkh::make_fastdiv((uint32_t)d->Wo);
   p.div_s = vkh::make_fastdiv((uint32_t)d->S);
@@ -396,7 +396,7 @@ int conv_wgrad_impl(const vk_conv_desc* d, const void* dz, float* dw, void* work
   return dispatch_w(d->dtype, p, cmin, workspace, workspace_bytes, st);
 }
 
-// ---- stem (7x7 stride 2, 3->64) weight gradient for the 16-bit types: one workgroup stages a 4 x 32 output-pixel tile of dz
+// ---- stem (7x7 stride 2, cin->64, 1 <= cin <= 4) weight gradient for the 16-bit types: one workgroup stages a 4 x 32 output-pixel tile of dz
 // and the 13 x 72 input pixels under it ONCE and accumulates all seven filter rows from them (the tap-by-tap kernel above
 // streams dz once per filter row: 7 passes over the 268 MB tensor).
 //   dW[k][r][s][c] = sum_px dz[px][k] * x4[2y + r - 3][2x + s - 3][c]
@@ -410,9 +410,10 @@ struct StemWgParams {
   const void* z;          // BNA form: dz is the masked upstream gradient g, the operand is a*g + b*z + c (BatchNorm backward apply, folded in)
   const float* coef;      // [3][64]: a, b, c
   float* dw;
-  float* slab;            // [gridDim.x][64 * 147] per-workgroup partial results (nullptr: fp32 atomics into dw)
+  float* slab;            // [gridDim.x][64 * 49 * cin] per-workgroup partial results (nullptr: fp32 atomics into dw)
   uint32_t x_bytes, dz_bytes;
   int N, H, W, Ho, Wo, tiles_x, tiles_y, ntiles;
+  int cin;                // channels of x4 that are data: dW is KRSC [64][7][7][cin], the columns ci >= cin are dropped
 };
 
 // BNA (r04): the stem's BatchNorm-backward apply pass exists only to feed this kernel (the stem has no data gradient): instead of
@@ -550,34 +551,35 @@ __global__ __launch_bounds__(256) void k_stem_wgrad(const StemWgParams p) {
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int sx = 4 * h + ((lane & 15) >> 2), ci = lane & 3;
-      if (sx < 7 && ci < 3) {
+      if (sx < 7 && ci < p.cin) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int k = wave * 16 + (lane >> 4) * 4 + e;
-          const size_t off = (((size_t)k * 7 + r) * 7 + sx) * 3 + ci;
-          if (p.slab) p.slab[(size_t)blockIdx.x * (64 * 147) + off] = acc[r][h][e];       // every workgroup writes all 9,408 elements
+          const size_t off = (((size_t)k * 7 + r) * 7 + sx) * p.cin + ci;
+          if (p.slab) p.slab[(size_t)blockIdx.x * (64 * 49 * p.cin) + off] = acc[r][h][e];       // every workgroup writes all 3,136 cin elements
           else atomicAdd(p.dw + off, acc[r][h][e]);
         }
       }
     }
 }
 
-int stem_wgrad_impl(vk_dtype dt, int N, int H, int W, const void* x4, const void* dz, float* dw, void* workspace, size_t workspace_bytes,
+int stem_wgrad_impl(vk_dtype dt, int N, int H, int W, int cin, const void* x4, const void* dz, float* dw, void* workspace, size_t workspace_bytes,
                     hipStream_t st, const void* bn_z = nullptr, const float* bn_coef = nullptr) {
   VK_CHECK_ARG(x4 && dz && dw, "vk_stem_wgrad: null argument");
+  VK_CHECK_ARG(cin >= 1 && cin <= 4, "vk_stem_wgrad_c: cin=%d is outside 1..4", cin);
   const int eb = dt == VK_F32 ? 4 : 2;
   const bool tile = dt != VK_F32 && !getenv("VK_STEM_WGRAD_TAPS") && (size_t)N * (H / 2) * (W / 2) * 64 * 2 < (1ull << 31);
   if (bn_z && !tile) return VK_ERR_UNSUPPORTED;        // the folded BatchNorm apply lives in the 16-bit tile kernel only
   if (tile) {
     StemWgParams q;
     q.x4 = x4; q.dz = dz; q.dw = dw; q.z = bn_z; q.coef = bn_coef;
-    q.N = N; q.H = H; q.W = W; q.Ho = H / 2; q.Wo = W / 2;
+    q.N = N; q.H = H; q.W = W; q.Ho = H / 2; q.Wo = W / 2; q.cin = cin;
     q.x_bytes = (uint32_t)((size_t)N * H * W * 4 * 2);
     q.dz_bytes = (uint32_t)((size_t)N * q.Ho * q.Wo * 64 * 2);
     q.tiles_x = (q.Wo + 31) / 32; q.tiles_y = (q.Ho + 3) / 4;
     q.ntiles = N * q.tiles_y * q.tiles_x;
     int nb = q.ntiles < 512 ? q.ntiles : 512;
-    const size_t out_elems = 64 * 147;
+    const size_t out_elems = (size_t)64 * 49 * cin;        // 3,136 cin: a multiple of 4 for every cin (the reduce adds 16-byte vectors)
     q.slab = nullptr;
     if (workspace && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0 && (reinterpret_cast<uintptr_t>(dw) & 15) == 0 &&
         workspace_bytes >= out_elems * 4 && !getenv("VK_WGRAD_ATOMICS")) {
@@ -585,8 +587,8 @@ int stem_wgrad_impl(vk_dtype dt, int N, int H, int W, const void* x4, const void
       if ((size_t)nb > cap) nb = (int)cap;
       q.slab = (float*)workspace;
     }
-    const double flops = 2.0 * (double)N * q.Ho * q.Wo * 64.0 * 147.0;
-    const double bytes = ((double)N * H * W * 4 + (double)N * q.Ho * q.Wo * 64 * (bn_z ? 2 : 1)) * 2.0 + 64.0 * 147 * 4;
+    const double flops = 2.0 * (double)N * q.Ho * q.Wo * 64.0 * 49.0 * cin;
+    const double bytes = ((double)N * H * W * 4 + (double)N * q.Ho * q.Wo * 64 * (bn_z ? 2 : 1)) * 2.0 + 64.0 * 49 * cin * 4;
     auto stem = [&](auto e) {
       using T = decltype(e);
       if (bn_z) return vkh::launch<k_stem_wgrad<T, true>>(dim3((unsigned)nb), dim3(256), 0, st, "wgrad_stem_16b_bn", {}, flops, bytes, q);
@@ -608,7 +610,7 @@ int stem_wgrad_impl(vk_dtype dt, int N, int H, int W, const void* x4, const void
   p.C = 32;
   p.M = N * p.Ho * p.Wo;
   p.RS = 7;
-  p.stem = 1;
+  p.stem = 1; p.cin = cin;
   p.div_hw = vkh::make_fastdiv((uint32_t)(p.Ho * p.Wo));
   p.div_w = vkh::make_fastdiv((uint32_t)p.Wo);
   p.div_s = vkh::make_fastdiv(1);
@@ -616,11 +618,11 @@ int stem_wgrad_impl(vk_dtype dt, int N, int H, int W, const void* x4, const void
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// Data gradient of the stem (the gradient of the model's input): the transpose of the 7x7 stride-2 pad-3 convolution, 64 -> 3
-// channels, in the space-to-depth form.  Output pixel (2i + u, 2j + v) receives dz[i - 1 + wy][j - 1 + wx][k] * w[k][r][s][c] with
+// Data gradient of the stem (the gradient of the model's input): the transpose of the 7x7 stride-2 pad-3 convolution, 64 -> cin
+// channels (1 <= cin <= 4), in the space-to-depth form.  Output pixel (2i + u, 2j + v) receives dz[i - 1 + wy][j - 1 + wx][k] * w[k][r][s][c] with
 // r = u + 5 - 2 wy, s = v + 5 - 2 wx (a tap exists where 0 <= r, s <= 6: 3 rows for u = 0, 4 for u = 1), so every 2x2 output block
-// (i, j) reads the same 4x4 window of dz.  One GEMM:  M = N * Ho * Wo blocks, K = 16 window positions x 64 channels, N = 12 outputs
-// (u, v, c) padded to 16, against a re-packed weight matrix of which 49 / 64 taps are non-zero.
+// (i, j) reads the same 4x4 window of dz.  One GEMM:  M = N * Ho * Wo blocks, K = 16 window positions x 64 channels, N = 4 cin outputs
+// (u, v, c) -> column uv * cin + c, padded to 16 (four channels fill it exactly), against a re-packed weight matrix of which 49 / 64 taps are non-zero.
 //   A (dz): lane (m = lane & 15, q = lane >> 4) holds block j0 + m, channels grp * 4 VE + q VE .. + VE - 1 of one window position:
 //           ONE 16-byte NHWC load per lane and MFMA step (16-bit: one 16x16x32; fp32: four 16x16x4, Mma<float>'s k permutation);
 //   B (weights): the same (window, group, lane) geometry, built once per workgroup in LDS from the fp32 KRSC master weights;
@@ -631,9 +633,9 @@ struct StemDgParams {
   const void* g;
   const void* z;
   const float* coef;      // [3][64] (BNA)
-  const float* w;         // fp32 KRSC [64][7][7][3]
-  float* dx;              // fp32 NCHW [N][3][H][W]
-  int N, H, W, Ho, Wo, tiles_x, tiles_y, ntiles;
+  const float* w;         // fp32 KRSC [64][7][7][cin]
+  float* dx;              // fp32 NCHW [N][cin][H][W]
+  int N, H, W, Ho, Wo, tiles_x, tiles_y, ntiles, cin;
 };
 
 template <typename T, bool BNA>
@@ -647,14 +649,14 @@ __global__ __launch_bounds__(256) void k_stem_dgrad(const StemDgParams p) {
   for (int sl = tid; sl < 16 * NG * 64; sl += 256) {
     const int ln = sl & 63, grp = (sl >> 6) % NG, win = sl / (64 * NG);
     const int n = ln & 15, wy = win >> 2, wx = win & 3;
-    const int uv = n / 3, c = n - 3 * uv;
+    const int uv = n / p.cin, c = n - p.cin * uv;
     const int r = (uv >> 1) + 5 - 2 * wy, s = (uv & 1) + 5 - 2 * wx;
-    const bool tap = n < 12 && r >= 0 && r <= 6 && s >= 0 && s <= 6;
+    const bool tap = n < 4 * p.cin && r >= 0 && r <= 6 && s >= 0 && s <= 6;
     float f[VE];
 #pragma unroll
     for (int j = 0; j < VE; ++j) {
       const int k = grp * CPG + (ln >> 4) * VE + j;
-      f[j] = tap ? p.w[((k * 7 + r) * 7 + s) * 3 + c] : 0.f;
+      f[j] = tap ? p.w[((k * 7 + r) * 7 + s) * p.cin + c] : 0.f;
     }
     Bs[sl] = Vec16<T>::pack(f);
   }
@@ -673,6 +675,7 @@ __global__ __launch_bounds__(256) void k_stem_dgrad(const StemDgParams p) {
   __syncthreads();
   const T* g = (const T*)p.g;
   const T* z = (const T*)p.z;
+  const int uv = m / p.cin, c = m - p.cin * uv;      // this lane's output column m = uv * cin + c (a store only where m < 4 cin)
   for (int t = blockIdx.x; t < p.ntiles; t += gridDim.x) {
     const int tx = t % p.tiles_x, ty = (t / p.tiles_x) % p.tiles_y, nimg = t / (p.tiles_x * p.tiles_y);
     const int i = ty * 4 + wave, j0 = tx * 16;
@@ -705,30 +708,30 @@ __global__ __launch_bounds__(256) void k_stem_dgrad(const StemDgParams p) {
         }
       }
     }
-    if (m < 12) {
-      const int uv = m / 3, c = m - 3 * uv;
-      float* dst = p.dx + (((size_t)nimg * 3 + c) * p.H + 2 * i + (uv >> 1)) * p.W + (uv & 1);
+    if (m < 4 * p.cin) {
+      float* dst = p.dx + (((size_t)nimg * p.cin + c) * p.H + 2 * i + (uv >> 1)) * p.W + (uv & 1);
 #pragma unroll
       for (int e = 0; e < 4; ++e) dst[2 * (j0 + 4 * q + e)] = acc[e];
     }
   }
 }
 
-static int stem_dgrad_impl(vk_dtype dt, int N, int H, int W, const void* g, const void* z, const float* coef, const float* w, float* dx,
+static int stem_dgrad_impl(vk_dtype dt, int N, int H, int W, int cin, const void* g, const void* z, const float* coef, const float* w, float* dx,
                            hipStream_t st) {
   VK_CHECK_ARG(g && w && dx && (!coef || z), "vk_stem_dgrad: null argument");
+  VK_CHECK_ARG(cin >= 1 && cin <= 4, "vk_stem_dgrad_c: cin=%d is outside 1..4", cin);
   VK_CHECK_ARG(N >= 1 && H >= 8 && W >= 32 && H % 8 == 0 && W % 32 == 0, "vk_stem_dgrad: H=%d W=%d (need H %% 8 == 0, W %% 32 == 0)", H, W);
   VK_CHECK_ARG(dt == VK_F32 || dt == VK_BF16 || dt == VK_F16, "vk_stem_dgrad: bad dtype");
   StemDgParams q;
   q.g = g; q.z = z; q.coef = coef; q.w = w; q.dx = dx;
-  q.N = N; q.H = H; q.W = W; q.Ho = H / 2; q.Wo = W / 2;
+  q.N = N; q.H = H; q.W = W; q.Ho = H / 2; q.Wo = W / 2; q.cin = cin;
   q.tiles_x = q.Wo / 16; q.tiles_y = q.Ho / 4;
   q.ntiles = N * q.tiles_x * q.tiles_y;
   const int cap = dt == VK_F32 ? 512 : 1024;            // persistent: every workgroup builds the weight table once
   const int nb = q.ntiles < cap ? q.ntiles : cap;
   const double eb = dt == VK_F32 ? 4.0 : 2.0;
   const double flops = 2.0 * (double)N * q.Ho * q.Wo * 1024.0 * 16.0;
-  const double bytes = (double)N * q.Ho * q.Wo * 64 * eb * (coef ? 2.0 : 1.0) + (double)N * 3 * H * W * 4.0;
+  const double bytes = (double)N * q.Ho * q.Wo * 64 * eb * (coef ? 2.0 : 1.0) + (double)N * cin * H * W * 4.0;
   return dispatch_dtype(dt, [&](auto e) {
     using T = decltype(e);
     if (coef) return vkh::launch<k_stem_dgrad<T, true>>(dim3((unsigned)nb), dim3(256), 0, st, "stem_dgrad_bn", {}, flops, bytes, q);
@@ -738,20 +741,32 @@ static int stem_dgrad_impl(vk_dtype dt, int N, int H, int W, const void* g, cons
 
 }  // namespace vk
 
+extern "C" int vk_stem_dgrad_c(vk_dtype dtype, int N, int H, int W, int cin, const void* g, const void* z, const float* coef_abc, const float* w_krsc,
+                               float* dx, void* stream) {
+  return vk::stem_dgrad_impl(dtype, N, H, W, cin, g, z, coef_abc, w_krsc, dx, (hipStream_t)stream);
+}
 extern "C" int vk_stem_dgrad(vk_dtype dtype, int N, int H, int W, const void* g, const void* z, const float* coef_abc, const float* w_krsc3,
                              float* dx, void* stream) {
-  return vk::stem_dgrad_impl(dtype, N, H, W, g, z, coef_abc, w_krsc3, dx, (hipStream_t)stream);
+  return vk_stem_dgrad_c(dtype, N, H, W, 3, g, z, coef_abc, w_krsc3, dx, stream);
 }
 
 extern "C" int vk_conv_wgrad(const vk_conv_desc* d, const void* dz, float* dw, void* workspace, size_t workspace_bytes, void* stream) {
   return vk::conv_wgrad_impl(d, dz, dw, workspace, workspace_bytes, (hipStream_t)stream);
 }
+extern "C" int vk_stem_wgrad_c(vk_dtype dtype, int N, int H, int W, int cin, const void* x4, const void* dz, float* dw_krsc, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+  return vk::stem_wgrad_impl(dtype, N, H, W, cin, x4, dz, dw_krsc, workspace, workspace_bytes, (hipStream_t)stream);
+}
 extern "C" int vk_stem_wgrad(vk_dtype dtype, int N, int H, int W, const void* x4, const void* dz, float* dw_krsc3, void* workspace,
                              size_t workspace_bytes, void* stream) {
-  return vk::stem_wgrad_impl(dtype, N, H, W, x4, dz, dw_krsc3, workspace, workspace_bytes, (hipStream_t)stream);
+  return vk_stem_wgrad_c(dtype, N, H, W, 3, x4, dz, dw_krsc3, workspace, workspace_bytes, stream);
+}
+extern "C" int vk_stem_wgrad_bn_c(vk_dtype dtype, int N, int H, int W, int cin, const void* x4, const void* g, const void* z, const float* coef_abc,
+                                  float* dw_krsc, void* workspace, size_t workspace_bytes, void* stream) {
+  VK_CHECK_ARG(z && coef_abc, "vk_stem_wgrad_bn: null argument");
+  return vk::stem_wgrad_impl(dtype, N, H, W, cin, x4, g, dw_krsc, workspace, workspace_bytes, (hipStream_t)stream, z, coef_abc);
 }
 extern "C" int vk_stem_wgrad_bn(vk_dtype dtype, int N, int H, int W, const void* x4, const void* g, const void* z, const float* coef_abc,
                                 float* dw_krsc3, void* workspace, size_t workspace_bytes, void* stream) {
-  VK_CHECK_ARG(z && coef_abc, "vk_stem_wgrad_bn: null argument");
-  return vk::stem_wgrad_impl(dtype, N, H, W, x4, g, dw_krsc3, workspace, workspace_bytes, (hipStream_t)stream, z, coef_abc);
+  return vk_stem_wgrad_bn_c(dtype, N, H, W, 3, x4, g, z, coef_abc, dw_krsc3, workspace, workspace_bytes, stream);
 }

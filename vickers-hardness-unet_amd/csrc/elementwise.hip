@@ -23,19 +23,19 @@ static inline int channel_grid(int blocks, int cv) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// K0: NCHW fp32 -> NHWC4 T
+// K0: NCHW fp32 [N][cin][H][W] -> NHWC4 T; channels >= cin are written as zero (1 <= cin <= 4, uniform over the launch)
 template <typename T>
-__global__ void k_input_transform(int N, int H, int W, const float* __restrict__ x, T* __restrict__ x4) {
+__global__ void k_input_transform(int N, int cin, int H, int W, const float* __restrict__ x, T* __restrict__ x4) {
   // grid.y = image; one 8- (16-bit types) or 16-byte store per pixel
   const size_t HW = (size_t)H * W;
-  const float* xn = x + (size_t)blockIdx.y * 3 * HW;
+  const float* xn = x + (size_t)blockIdx.y * cin * HW;
   T* on = x4 + (size_t)blockIdx.y * HW * 4;
   for (size_t hw = blockIdx.x * (size_t)blockDim.x + threadIdx.x; hw < HW; hw += (size_t)gridDim.x * blockDim.x) {
-    const float r = xn[hw], g = xn[HW + hw], b = xn[2 * HW + hw];
+    const float r = xn[hw], g = cin > 1 ? xn[HW + hw] : 0.f, b = cin > 2 ? xn[2 * HW + hw] : 0.f, a = cin > 3 ? xn[3 * HW + hw] : 0.f;
     if constexpr (sizeof(T) == 4) {
-      *reinterpret_cast<f32x4_t*>(on + hw * 4) = f32x4_t{r, g, b, 0.f};
+      *reinterpret_cast<f32x4_t*>(on + hw * 4) = f32x4_t{r, g, b, a};
     } else {
-      float f[8] = {r, g, b, 0.f, 0.f, 0.f, 0.f, 0.f};
+      float f[8] = {r, g, b, a, 0.f, 0.f, 0.f, 0.f};
       const u32x4_t pk = Vec16<T>::pack(f);
       *reinterpret_cast<u32x2_t*>(on + hw * 4) = u32x2_t{pk[0], pk[1]};
     }
@@ -1246,12 +1246,75 @@ static int check_flat_channels(const char* fn, int C) {
   return VK_OK;
 }
 
-extern "C" int vk_input_transform(vk_dtype dtype, int N, int H, int W, const float* x, void* x4, void* stream) {
+extern "C" int vk_input_transform_c(vk_dtype dtype, int N, int cin, int H, int W, const float* x, void* x4, void* stream) {
   VK_CHECK_ARG(x && x4 && N > 0 && H > 0 && W > 0, "vk_input_transform: bad argument");
-  hipStream_t st = (hipStream_t)stream;
-  vkh::ProfScope ps_("input_transform", st, 0.0, (double)N * H * W * (12.0 + 4.0 * (dtype == VK_F32 ? 4.0 : 2.0)));
+  VK_CHECK_ARG(cin >= 1 && cin <= 4, "vk_input_transform_c: cin=%d is outside 1..4", cin);
+  VK_CHECK_ARG(dtype == VK_F32 || dtype == VK_BF16 || dtype == VK_F16, "vk_input_transform: bad dtype %d", (int)dtype);
   VK_CHECK_ARG(N <= 65535, "vk_input_transform: N too large for the launch grid");
-  DISPATCH_T(dtype, hipLaunchKernelGGL(k_input_transform<T>, dim3(grid_for((size_t)H * W, 256, 1024), (unsigned)N), dim3(256), 0, st, N, H, W, x, (T*)x4));
+  hipStream_t st = (hipStream_t)stream;
+  vkh::ProfScope ps_("input_transform", st, 0.0, (double)N * H * W * (4.0 * cin + 4.0 * (dtype == VK_F32 ? 4.0 : 2.0)));
+  DISPATCH_T(dtype, hipLaunchKernelGGL(k_input_transform<T>, dim3(grid_for((size_t)H * W, 256, 1024), (unsigned)N), dim3(256), 0, st, N, cin, H, W, x, (T*)x4));
+  VK_CHECK_HIP(hipGetLastError());
+  return VK_OK;
+}
+extern "C" int vk_input_transform(vk_dtype dtype, int N, int H, int W, const float* x, void* x4, void* stream) {
+  return vk_input_transform_c(dtype, N, 3, H, W, x, x4, stream);
+}
+
+// ------------------------------------------------------------------------------------------------
+// vk_input_mix: out[n][o][p] = b[o] + M[o][0] x0 + M[o][1] x1 + M[o][2] x2 over the planes of a normalised 3-channel fp32 NCHW batch
+// (the bridge from the device data path to a model of 1..4 input channels).  One read of each input plane, one write per output plane.
+namespace vk {
+struct InputMixParams {
+  float m[4][3];
+  float b[4];
+};
+
+template <int VEC>
+__global__ __launch_bounds__(256) void k_input_mix(int cout, size_t hw, const float* __restrict__ x3, float* __restrict__ out, const InputMixParams q) {
+  // grid.y = image; VEC = 4: hw % 4 == 0 and both tensors 16-byte aligned, so every plane start is; VEC = 1: element accesses
+  const float* xn = x3 + (size_t)blockIdx.y * 3 * hw;
+  float* on = out + (size_t)blockIdx.y * cout * hw;
+  const size_t nv = hw / VEC;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < nv; i += (size_t)gridDim.x * blockDim.x) {
+    float a0[VEC], a1[VEC], a2[VEC];
+    if constexpr (VEC == 4) {
+      const f32x4_t v0 = *reinterpret_cast<const f32x4_t*>(xn + i * 4);
+      const f32x4_t v1 = *reinterpret_cast<const f32x4_t*>(xn + hw + i * 4);
+      const f32x4_t v2 = *reinterpret_cast<const f32x4_t*>(xn + 2 * hw + i * 4);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) { a0[j] = v0[j]; a1[j] = v1[j]; a2[j] = v2[j]; }
+    } else {
+      a0[0] = xn[i]; a1[0] = xn[hw + i]; a2[0] = xn[2 * hw + i];
+    }
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+      if (o >= cout) break;
+      float r[VEC];
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) r[j] = fmaf(q.m[o][2], a2[j], fmaf(q.m[o][1], a1[j], fmaf(q.m[o][0], a0[j], q.b[o])));
+      if constexpr (VEC == 4) *reinterpret_cast<f32x4_t*>(on + (size_t)o * hw + i * 4) = f32x4_t{r[0], r[1], r[2], r[3]};
+      else on[(size_t)o * hw + i] = r[0];
+    }
+  }
+}
+}  // namespace vk
+
+extern "C" int vk_input_mix(int N, int cout, size_t hw, const float* x3, const float* M, const float* b, float* out, void* stream) {
+  VK_CHECK_ARG(x3 && M && out, "vk_input_mix: null argument");
+  VK_CHECK_ARG(N >= 1 && N <= 65535 && hw >= 1, "vk_input_mix: N=%d, hw=%zu", N, hw);
+  VK_CHECK_ARG(cout >= 1 && cout <= 4, "vk_input_mix: cout=%d is outside 1..4", cout);
+  VK_CHECK_ARG((reinterpret_cast<uintptr_t>(x3) & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0, "vk_input_mix: unaligned fp32 pointer");
+  vk::InputMixParams q;                       // M [cout][3] and b [cout] (NULL: zero) are HOST arrays, passed by value
+  for (int o = 0; o < 4; ++o) {
+    for (int j = 0; j < 3; ++j) q.m[o][j] = o < cout ? M[o * 3 + j] : 0.f;
+    q.b[o] = o < cout && b ? b[o] : 0.f;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const bool vec = hw % 4 == 0 && ((reinterpret_cast<uintptr_t>(x3) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+  vkh::ProfScope ps_("input_mix", st, 0.0, (double)N * (double)hw * 4.0 * (3.0 + cout));
+  if (vec) hipLaunchKernelGGL(vk::k_input_mix<4>, dim3(grid_for(hw / 4, 256, 1024), (unsigned)N), dim3(256), 0, st, cout, hw, x3, out, q);
+  else hipLaunchKernelGGL(vk::k_input_mix<1>, dim3(grid_for(hw, 256, 1024), (unsigned)N), dim3(256), 0, st, cout, hw, x3, out, q);
   VK_CHECK_HIP(hipGetLastError());
   return VK_OK;
 }

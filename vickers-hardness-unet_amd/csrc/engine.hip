@@ -2,6 +2,7 @@
 // kernels in this directory.  Mirrors the reference composition: train.py:372-378 (constructor
 // arguments), train.py:436 (forward), :438 (BCE + Dice), :443/:448 (backward); topology restated
 // from smp.  Host-only code except for the small weight-packing kernels.
+// vk_unet_create_ex / _enc / _in widen classes (1..16), the encoder (resnet18 / 34 / 50) and in_channels (1..4) of that plan.
 //
 // Memory model: the caller owns four flat buffers (fp32 params, fp32 grads, fp32 BN running stats,
 // int64 num_batches_tracked) plus one workspace; this file only computes offsets into them.
@@ -283,14 +284,14 @@ __global__ void k_cast_ranges(const CastRange* __restrict__ tab, const float* __
     st1(dst + r.begin + i, src[r.begin + i]);
 }
 
-// stem pack: wp[k][r][s*4 + c] = w[k][r][s][c] (s < 7, c < 3), zero elsewhere;  w is KRSC [64][7][7][3]
+// stem pack: wp[k][r][s*4 + c] = w[k][r][s][c] (s < 7, c < cin), zero elsewhere;  w is KRSC [64][7][7][cin], 1 <= cin <= 4
 template <typename T>
-__global__ void k_pack_stem(const float* __restrict__ w, T* __restrict__ wp) {
+__global__ void k_pack_stem(const float* __restrict__ w, T* __restrict__ wp, int cin) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= 64 * 7 * 32) return;
   const int j = i % 32, r = (i / 32) % 7, k = i / (32 * 7);
   const int s = j >> 2, c = j & 3;
-  const float v = (s < 7 && c < 3) ? w[((k * 7 + r) * 7 + s) * 3 + c] : 0.f;
+  const float v = (s < 7 && c < cin) ? w[((k * 7 + r) * 7 + s) * cin + c] : 0.f;
   st1(wp + i, v);
 }
 
@@ -435,6 +436,7 @@ struct vk_unet {
   vk_unet_config cfg;
   int classes = 1;               // output channels of the head (vk_unet_create_ex); 1 is the binary model and its kernels
   const EncoderTopo* enc = nullptr;   // vk_unet_create_enc; resnet34 for vk_unet_create / vk_unet_create_ex
+  int in_channels = 3;           // channels of the input image (vk_unet_create_in: 1..4); 3 is the reference's model
   int sink_c = 512;              // gamma / beta slots of the frozen-gradient sink: the widest BatchNorm (resnet34 keeps 512)
   int eb;                        // element bytes of the activation dtype
   std::vector<vk_tensor_info> infos;
@@ -589,7 +591,10 @@ void build_topology(vk_unet* h) {
   const int S = h->cfg.size, SW = h->cfg.width, N = h->cfg.N;
   auto cnt = [&](int Hres, int Wres) { return (double)N * Hres * Wres; };
   // --- encoder stem
-  h->stem_conv = add_conv(h, "encoder.conv1", 3, 64, 7, 2, 3, S, SW);
+  // The stem weight is the first tensor of the flat buffer: 64 * 49 * in_channels floats, so every later tensor sits 3,136 * (in_channels
+  // - 3) floats from its place in the 3-channel model.  3,136 is a multiple of 4: each 16-byte alignment the kernels assume of a tensor's
+  // offset (add_conv rounds to 4 floats; the vector loads of the packs and of the optimizer) holds for every channel count.
+  h->stem_conv = add_conv(h, "encoder.conv1", h->in_channels, 64, 7, 2, 3, S, SW);
   h->convs[h->stem_conv].bn = add_bn(h, "encoder.bn1", 64, cnt(S / 2, SW / 2));
   // --- encoder layers
   const EncoderTopo& E = *h->enc;
@@ -973,7 +978,12 @@ extern "C" int vk_unet_create_ex(const vk_unet_config* cfg, int classes, vk_unet
 }
 
 extern "C" int vk_unet_create_enc(const vk_unet_config* cfg, int classes, int encoder, vk_unet** out) {
+  return vk_unet_create_in(cfg, classes, encoder, 3, out);
+}
+
+extern "C" int vk_unet_create_in(const vk_unet_config* cfg, int classes, int encoder, int in_channels, vk_unet** out) {
   VK_CHECK_ARG(cfg && out, "vk_unet_create: null argument");
+  VK_CHECK_ARG(in_channels >= 1 && in_channels <= 4, "vk_unet_create_in: in_channels=%d is outside 1..4 (the stem reads NHWC4)", in_channels);
   const EncoderTopo* enc = find_encoder(encoder);
   VK_CHECK_ARG(enc, "vk_unet_create_enc: encoder %d is not one of VK_ENC_RESNET18 / 34 / 50", encoder);
   VK_CHECK_ARG(classes >= 1 && classes <= 16, "vk_unet_create_ex: classes=%d is outside 1..16 (one 16-wide tile of head outputs)", classes);
@@ -985,6 +995,7 @@ extern "C" int vk_unet_create_enc(const vk_unet_config* cfg, int classes, int en
   h->cfg = *cfg;
   h->classes = classes;
   h->enc = enc;
+  h->in_channels = in_channels;
   h->cfg.width = width;
   h->eb = cfg->dtype == VK_F32 ? 4 : 2;
   build_topology(h);
@@ -1003,6 +1014,7 @@ extern "C" int vk_unet_create_enc(const vk_unet_config* cfg, int classes, int en
 
 extern "C" int vk_unet_num_classes(const vk_unet* h) { return h ? h->classes : 0; }
 extern "C" int vk_unet_encoder(const vk_unet* h) { return h ? h->enc->code : 0; }
+extern "C" int vk_unet_in_channels(const vk_unet* h) { return h ? h->in_channels : 0; }
 
 extern "C" void vk_unet_destroy(vk_unet* h) {
   if (!h) return;
@@ -1126,7 +1138,7 @@ static int refresh_t(vk_unet* h, hipStream_t st) {
     hipLaunchKernelGGL(k_pack_halo_tab<T>, dim3(32, (unsigned)h->halo_tab.size()), dim3(256), 0, st,
                        (const HaloPackEntry*)(h->ws + h->off_tab_halo), h->params, h->ws);
   hipLaunchKernelGGL(k_pack_stem<T>, dim3((64 * 7 * 32 + 255) / 256), dim3(256), 0, st,
-                     h->params + h->convs[h->stem_conv].w_off, (T*)(h->ws + h->off_wstem));
+                     h->params + h->convs[h->stem_conv].w_off, (T*)(h->ws + h->off_wstem), h->in_channels);
   VK_CHECK_HIP(hipGetLastError());
   return VK_OK;
 }
@@ -1225,7 +1237,7 @@ extern "C" int vk_unet_forward(vk_unet* h, const float* x, float* logits, int tr
   }
   // stem
   void* x4 = h->ws + h->off_x4;
-  RET_IF(vk_input_transform(dt, N, S, SW, x, x4, st));
+  RET_IF(vk_input_transform_c(dt, N, h->in_channels, S, SW, x, x4, st));
   ConvL& stem = h->convs[h->stem_conv];
   BnL& sbn = h->bns[stem.bn];
   RET_IF(vk_stem_fwd(dt, N, S, SW, x4, h->ws + h->off_wstem, stem.z, training && !frozen(h, sbn) ? sbn.stats : nullptr, st));
@@ -1722,11 +1734,11 @@ int backward_stem(vk_unet* h, hipStream_t st) {
       if (want_w) {
         hipStream_t ws;
         RET_IF(wgrad_stream(h, st, &ws));
-        rc = vk_stem_wgrad_bn(h->cfg.dtype, N, S, SW, h->ws + h->off_x4, stem.g, stem.z, b.coef, h->grads + stem.w_off,
+        rc = vk_stem_wgrad_bn_c(h->cfg.dtype, N, S, SW, h->in_channels, h->ws + h->off_x4, stem.g, stem.z, b.coef, h->grads + stem.w_off,
                               h->ws + h->off_wslab, VK_WGRAD_WORKSPACE_BYTES, ws);
         if (rc != VK_OK && rc != VK_ERR_UNSUPPORTED) return rc;
       }
-      if (rc == VK_OK) return h->dx_in ? vk_stem_dgrad(h->cfg.dtype, N, S, SW, stem.g, stem.z, b.coef, w, h->dx_in, st) : VK_OK;
+      if (rc == VK_OK) return h->dx_in ? vk_stem_dgrad_c(h->cfg.dtype, N, S, SW, h->in_channels, stem.g, stem.z, b.coef, w, h->dx_in, st) : VK_OK;
       // (shape outside the tile kernel: coefficients are in place, finish with the separate apply pass)
       RET_IF(vk_bn_bwd_apply(h->cfg.dtype, (size_t)N * (S / 2) * (SW / 2), 64, stem.g, stem.z, 0, b.scale, b.shift, nullptr, b.coef, stem.g, nullptr, 0, st));
     } else {
@@ -1736,9 +1748,9 @@ int backward_stem(vk_unet* h, hipStream_t st) {
   if (want_w) {
     hipStream_t ws;
     RET_IF(wgrad_stream(h, st, &ws));
-    RET_IF(vk_stem_wgrad(h->cfg.dtype, N, S, SW, h->ws + h->off_x4, stem.g, h->grads + stem.w_off, h->ws + h->off_wslab, VK_WGRAD_WORKSPACE_BYTES, ws));
+    RET_IF(vk_stem_wgrad_c(h->cfg.dtype, N, S, SW, h->in_channels, h->ws + h->off_x4, stem.g, h->grads + stem.w_off, h->ws + h->off_wslab, VK_WGRAD_WORKSPACE_BYTES, ws));
   }
-  return h->dx_in ? vk_stem_dgrad(h->cfg.dtype, N, S, SW, stem.g, nullptr, nullptr, w, h->dx_in, st) : VK_OK;
+  return h->dx_in ? vk_stem_dgrad_c(h->cfg.dtype, N, S, SW, h->in_channels, stem.g, nullptr, nullptr, w, h->dx_in, st) : VK_OK;
 }
 
 // the collected weight gradients of a stage: one batched launch (tables built once per stage and per workgroup budget), a single one

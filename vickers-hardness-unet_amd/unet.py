@@ -3,7 +3,7 @@ as the reference builds it (train.py:357-379 ``build_model``; infer_pth_gui.py:3
 ``Segmenter``), executed by the HIP engine in libvkunet.so.
 
 API surface kept: constructor arguments, ``forward(x[N,3,S,S] fp32) -> logits
-[N,1,S,S] fp32`` (``vk.multiclass.Unet``: ``classes=C``, 1 <= C <= 16, logits [N,C,S,S]), ``train()/eval()``, ``.to(device)``, ``parameters()``, ``state_dict()`` /
+[N,1,S,S] fp32`` (``vk.multiclass.Unet``: ``classes=C``, 1 <= C <= 16, logits [N,C,S,S]; ``vk.inputs.Unet``: ``in_channels=c``, 1 <= c <= 4, x [N,c,S,S]), ``train()/eval()``, ``.to(device)``, ``parameters()``, ``state_dict()`` /
 ``load_state_dict(strict=True)`` with smp's 278 keys (conv weights are logical OIHW tensors whose memory
 is KRSC = torch channels_last, all living in one flat fp32 buffer), autograd participation
 (``loss.backward()`` fills ``p.grad``), ``torch.autocast`` selects the 16-bit plan exactly where the
@@ -54,7 +54,8 @@ class _Plan:
         self.weights_version = None
         self.mask = None                    # trainable flags the engine holds (vk_unet_set_trainable); None: not pushed yet
         self.bn_frozen = None               # BatchNorm modes the engine holds (vk_unet_set_bn_frozen); None: not pushed (all train)
-        self.dx: Optional[torch.Tensor] = None     # fp32 [N,3,H,W] input gradient the engine writes (vk_unet_set_input_grad)
+        self.in_channels = model.in_channels
+        self.dx: Optional[torch.Tensor] = None     # fp32 [N,in_channels,H,W] input gradient the engine writes (vk_unet_set_input_grad)
         self.dx_on = False
         self.serial = 0                     # forwards this plan has run; a graph remembers the value its own forward left (_UnetFn)
         self.last_forward = ""              # what ran that forward, for the message of a displaced graph
@@ -97,7 +98,7 @@ class _Plan:
         if on == self.dx_on:
             return
         if on and self.dx is None:
-            self.dx = torch.empty(self.N, 3, self.H, self.W, dtype=torch.float32, device=device)
+            self.dx = torch.empty(self.N, self.in_channels, self.H, self.W, dtype=torch.float32, device=device)
         check(lib().vk_unet_set_input_grad(self.h, self.dx.data_ptr() if on else None), "vk_unet_set_input_grad")
         self.dx_on = on
 
@@ -169,6 +170,7 @@ class _UnetFn(torch.autograd.Function):
 class Unet(nn.Module):
     max_classes = 1                # the reference's binary model; vk.multiclass.Unet takes 1 <= classes <= 16
     encoders = ("resnet34",)       # the reference's encoder; vk.encoders.Unet also builds resnet18 and resnet50
+    in_channels_allowed = (3,)     # the reference's colour input; vk.inputs.Unet takes 1 <= in_channels <= 4
 
     def __init__(self, encoder_name: str = "resnet34", encoder_depth: int = 5, encoder_weights: Optional[str] = "imagenet",
                  decoder_use_batchnorm: bool = True, decoder_channels=(256, 128, 64, 32, 16),
@@ -184,10 +186,11 @@ class Unet(nn.Module):
             raise VkError("encoder_weights=%r needs a checkpoint download; no network here — pass None and "
                           "load_state_dict() a checkpoint instead" % (encoder_weights,))
         if (encoder_depth != 5 or tuple(decoder_channels) != (256, 128, 64, 32, 16) or not decoder_use_batchnorm
-                or decoder_attention_type is not None or in_channels != 3 or activation is not None
+                or decoder_attention_type is not None or in_channels not in self.in_channels_allowed or activation is not None
                 or aux_params is not None):
-            raise NotImplementedError("only in_channels=3, activation=None, default decoder are implemented "
-                                      "(reference train.py:372-378)")
+            chans = "=3" if self.in_channels_allowed == (3,) else " in %s" % (self.in_channels_allowed,)
+            raise NotImplementedError("only in_channels%s, activation=None, default decoder are implemented "
+                                      "(reference train.py:372-378)" % chans)
         if not isinstance(classes, int) or not 1 <= classes <= self.max_classes:
             if self.max_classes == 1:
                 raise NotImplementedError("classes=%r: vk.Unet is the reference's binary model (classes=1); more than one class: "
@@ -195,6 +198,7 @@ class Unet(nn.Module):
             raise NotImplementedError("classes=%r: 1 <= classes <= %d is implemented (the head is one 16-wide tile of output "
                                       "channels)" % (classes, self.max_classes))
         self.classes = classes
+        self.in_channels = int(in_channels)
         self.encoder_name = encoder_name
         self.compute_dtype = compute_dtype
         L = lib()
@@ -231,12 +235,16 @@ class Unet(nn.Module):
 
     # ------------------------------------------------------------------ structure
     def _create_handle(self, cfg, h):
-        """Engine plan of this model's encoder and classes (vk_unet_create_ex: resnet34; vk_unet_create_enc: the others)."""
-        if self.encoder_name == "resnet34":
+        """Engine plan of this model's encoder, classes and input channels (vk_unet_create_ex: resnet34; vk_unet_create_enc: the other
+        encoders; vk_unet_create_in: in_channels other than 3)."""
+        codes = {"resnet18": _lib.VK_ENC_RESNET18, "resnet34": _lib.VK_ENC_RESNET34, "resnet50": _lib.VK_ENC_RESNET50}
+        if self.in_channels != 3:
+            check(lib().vk_unet_create_in(C.byref(cfg), self.classes, codes[self.encoder_name], self.in_channels, C.byref(h)),
+                  "vk_unet_create_in")
+        elif self.encoder_name == "resnet34":
             check(lib().vk_unet_create_ex(C.byref(cfg), self.classes, C.byref(h)), "vk_unet_create_ex")
         else:
-            code = {"resnet18": _lib.VK_ENC_RESNET18, "resnet50": _lib.VK_ENC_RESNET50}[self.encoder_name]
-            check(lib().vk_unet_create_enc(C.byref(cfg), self.classes, code, C.byref(h)), "vk_unet_create_enc")
+            check(lib().vk_unet_create_enc(C.byref(cfg), self.classes, codes[self.encoder_name], C.byref(h)), "vk_unet_create_enc")
 
     def _view(self, kind: int, dims: List[int], off: int, numel: int, which: str = "params") -> torch.Tensor:
         if kind == 0:
@@ -329,13 +337,24 @@ class Unet(nn.Module):
                     if t[0]:
                         block.append((prefix, t))
                 return out
+            # torchvision builds its ResNet with 3 input channels whatever in_channels is (smp patches conv1 afterwards, below)
+            def tv_shape(t):
+                return [t[2][0], 3] + t[2][2:] if t[0] == "encoder.conv1.weight" else t[2]
             for t in ctor_order(enc):
-                ctor_draw(t[2])
+                ctor_draw(tv_shape(t))
             ctor_draw([1000, enc[-1][2][0]], bias=True)        # the fc layer torchvision builds and smp deletes (512 x expansion inputs)
             for t in enc:                                      # ResNet.__init__ init loop (module order)
-                w = torch.empty(t[2])
+                w = torch.empty(tv_shape(t))
                 nn.init.kaiming_normal_(w, mode="fan_out", nonlinearity="relu")
-                sd[t[0]].copy_(w)
+                if t[0] != "encoder.conv1.weight" or self.in_channels == 3:      # otherwise smp replaces this tensor, below
+                    sd[t[0]].copy_(w)
+            if self.in_channels != 3:
+                # smp get_encoder -> set_in_channels(in_channels, pretrained=False) -> patch_first_conv: conv1.weight becomes a fresh
+                # [64][in_channels][7][7] tensor and reset_parameters() draws it (kaiming_uniform_, a = sqrt(5)): one more draw, behind
+                # the encoder's init loop and before the decoder exists.  Recalled from upstream source; no fixture pins it
+                w = torch.empty(enc[0][2])
+                nn.init.kaiming_uniform_(w, a=math.sqrt(5))
+                sd[enc[0][0]].copy_(w)
             for t in dec:
                 ctor_draw(t[2])
             ctor_draw(head[2], bias=True)
@@ -412,8 +431,8 @@ class Unet(nn.Module):
         return p
 
     def _check_input(self, x: torch.Tensor):
-        if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.shape[1] != 3:
-            raise ValueError("expected input [N,3,H,W], got %s" % (tuple(x.shape),))
+        if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.shape[1] != self.in_channels:
+            raise ValueError("expected input [N,%d,H,W], got %s" % (self.in_channels, tuple(x.shape)))
         h, w = x.shape[-2:]
         if h % 32 or w % 32:
             raise RuntimeError(f"Wrong input shape height={h}, width={w}. Expected image height and width divisible by 32.")

@@ -43,6 +43,8 @@
  *                                               reference trains on letterboxed images only)
  *   vk_cp_boxes / vk_cp_alpha / vk_cp_paste ... instance copy-paste between the letterboxed items (no counterpart: the reference never
  *                                               composes images)
+ *   vk_mg_render .............................. synthetic indentation micrographs with exact masks, rendered into the uint8 slot that
+ *                                               vk_augment_batch reads (no counterpart: the reference has its 183 photographs)
  *   vk_edt_sq / vk_boundary_phi / _stats / _loss  distance maps, surface-distance metrics and the boundary loss (no counterpart)
  *
  * Conventions
@@ -574,6 +576,91 @@ int vk_cp_alpha(int batch, int h, int w, const int32_t* slots, uint8_t* kept, ui
 int vk_cp_paste(int n, int S, int n_items, const uint8_t* images_rgb, const uint8_t* masks, const uint8_t* kept, const uint8_t* alpha,
                 const int32_t* base_index_dev, const int32_t* counts_host, const vk_cp_rec* recs_host, void* recs_dev, uint8_t* out_rgb,
                 uint8_t* out_mask, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Synthetic micrographs: scenes of Vickers indentations rendered on the device into uint8 pixels [n][S][S][3] and a
+ * {0, 1} mask [n][S][S] — the buffers vk_augment_batch reads.  A scene is one fixed-layout record set per image; all geometry is
+ * fixed point, 1/16 pixel, int32, the centre of pixel (x, y) being (16 x, 16 y).  All arithmetic is integer: the outputs are the bytes
+ * tests/micrographs_ref.py gives again.  Formulas (>> is the arithmetic shift, / the division of non-negative integers):
+ *   mix(h): h ^= h >> 16; h *= 0x7feb352d; h ^= h >> 15; h *= 0x846ca68b; h ^= h >> 16 (uint32).
+ *   Background level of pixel (x, y), any integers:  L = base + ((grad_x (x - grad_cx) + grad_y (y - grad_cy)) >> 8)
+ *     - ((vig ((x - vig_cx)^2 + (y - vig_cy)^2)) >> 16) + T,  T = ((val - 128) tex_amp) >> 8, val the bilinear lattice noise:
+ *     u = x tex_cos + y tex_sin, v = y tex_cos - x tex_sin (Q14); iu = u >> (14 + tex_lu), fu = (u >> (6 + tex_lu)) & 255, iv, fv
+ *     alike with tex_lv; g(i, j) = mix(i * 0x9E3779B1 + j * 0x85EBCA77 + tex_seed) & 255;
+ *     val = ((g(iu, iv) (256 - fu) + g(iu + 1, iv) fu) (256 - fv) + (g(iu, iv + 1) (256 - fu) + g(iu + 1, iv + 1) fu) fv + 32768) >> 16.
+ *   Scratches, in list order: with q = (16 x - s.x, 16 y - s.y), c = q.x s.dy - q.y s.dx, t = q.x s.dx + q.y s.dy: the pixel is
+ *     covered iff c^2 <= hw^2 (dx^2 + dy^2) and t0 <= t <= t1; L += depth.
+ *   Blobs: d2 = |q|^2 from the centre; if d2 < r^2: L -= (dark min(256, (r^2 - d2) / (r^2 >> 8))) >> 8.
+ *   Indentations, in list order, e_i = v_(i+1) - v_i, cr(a, b) = a.x b.y - a.y b.x:
+ *     inside (the mask) iff cr(e_i, p - v_i) >= 0 for the four i.  Inside, the facet f is the one i with cr(v_i - a, p - a) >= 0 and
+ *     cr(v_(i+1) - a, p - a) < 0 (p = a: facet 0); k = 256 cr(e_f, p - v_f) / cr(e_f, a - v_f) (0 at the edge, 256 at the apex);
+ *     L = shade[f] + ((slope[f] k) >> 8) + (T >> 1), and L += ridge if for some i, with w = v_i - a, q = p - a:
+ *     0 <= q.w <= |w|^2 and cr(w, q)^2 <= ridge_hw^2 |w|^2.
+ *     Outside, when halo_r > 0: d2 = min over the edges of the squared distance to the segment (cr^2 / |e|^2 where the foot lies on
+ *     it, else to the nearer end); if d2 < halo_r^2: L -= (halo_depth min(256, (halo_r^2 - d2) / (halo_r^2 >> 8))) >> 8.
+ *   Channel c of the ideal image: clamp((L tint[c] + 128) >> 8, 0, 255).
+ *   Optics: the separable binomial of radius blur_r (weights C(2 r, k), sum 4^r per axis) over the ideal image, which is defined
+ *     beyond the frame by the same formulas; (acc + (16^r >> 1)) >> 4 r.  Then noise: h = mix(((y S + x) 3 + c) * 0x9E3779B1 +
+ *     noise_seed), t = the sum of the four bytes of h - 510, value = clamp(value + ((t noise_amp + 128) >> 8), 0, 255).
+ *   Rects, in list order, after blur and noise, never in the mask: pixels with x0 <= x <= x1, y0 <= y <= y1, all of them when
+ *     thickness = 0, else those not inside (x0 + th .. x1 - th, y0 + th .. y1 - th); the colour replaces the pixel.
+ * One launch; a workgroup owns a 64 x 16 tile, evaluates the ideal image over the tile and a 3-pixel apron in LDS, blurs out of LDS and
+ * writes every output byte exactly once: no atomics, no workspace but scenes_dev (VK_MG_SCENES_DEV_BYTES(n), 4-byte aligned).
+ * Host checks (VK_ERR_ARG before anything touches the stream): no null buffer, buffers 4-byte aligned, n 1..65535, S in
+ * 16..VK_MG_MAX_SIDE, scenes_dev_bytes, every count within its limit, and per used record the ranges that keep every product inside
+ * int64 (VK_MG_MAX_SIDE is the largest S for which they do): coordinates in [-VK_MG_COORD_MARGIN, 16 S + VK_MG_COORD_MARGIN], a
+ * convex clockwise quadrilateral (cr(e_i, e_(i+1)) > 0, x to the right, y down), the apex strictly inside it, half widths and radii in
+ * 0..32767 (a blob's and a non-zero halo's from 16), |dx|, |dy| <= 16384 and not both 0, levels in -1024..1024, gains 0..1024, vig and
+ * noise_amp 0..255, tex_lu and tex_lv 0..8, |tex_cos|, |tex_sin| <= 16384, the gradient's and the vignette's centre in [-512, S + 512]
+ * pixels, rect corners within +-4096 pixels, blur_r 0..3.
+ * ---------------------------------------------------------------------------------------------- */
+#define VK_MG_MAX_INDENTS 8
+#define VK_MG_MAX_SCRATCHES 64
+#define VK_MG_MAX_BLOBS 8
+#define VK_MG_MAX_RECTS 4
+#define VK_MG_MAX_SIDE 1024
+#define VK_MG_MIN_SIDE 16
+#define VK_MG_COORD_MARGIN 8192
+typedef struct vk_mg_indent {
+  int32_t vx[4], vy[4];         /* vertices, clockwise */
+  int32_t ax, ay;               /* apex */
+  int32_t shade[4], slope[4];   /* facet i lies between the apex and the edge v_i v_(i+1) */
+  int32_t ridge, ridge_hw;      /* level added along the four apex-to-vertex segments, and their half width */
+  int32_t halo_r, halo_depth;
+  int32_t reserved[2];
+} vk_mg_indent;
+typedef struct vk_mg_scratch {
+  int32_t x, y, dx, dy;         /* a point and the direction (Q14 cosines) */
+  int32_t hw, depth;
+  int32_t t0, t1;               /* extent along the direction, in units of 1/16 pixel times |d|; INT32_MIN / INT32_MAX: none */
+} vk_mg_scratch;
+typedef struct vk_mg_blob {
+  int32_t x, y, r, dark;
+} vk_mg_blob;
+typedef struct vk_mg_rect {
+  int32_t x0, y0, x1, y1;       /* whole pixels, inclusive */
+  int32_t thickness;            /* 0: filled */
+  int32_t color[3];
+} vk_mg_rect;
+typedef struct vk_mg_scene {
+  int32_t n_indents, n_scratches, n_blobs, n_rects;
+  int32_t base, tint[3];
+  int32_t grad_x, grad_y, grad_cx, grad_cy;
+  int32_t vig_cx, vig_cy, vig;
+  int32_t tex_amp, tex_cos, tex_sin, tex_lu, tex_lv;
+  uint32_t tex_seed;
+  int32_t blur_r, noise_amp;
+  uint32_t noise_seed;
+  int32_t reserved[8];
+  vk_mg_indent indents[VK_MG_MAX_INDENTS];
+  vk_mg_scratch scratches[VK_MG_MAX_SCRATCHES];
+  vk_mg_blob blobs[VK_MG_MAX_BLOBS];
+  vk_mg_rect rects[VK_MG_MAX_RECTS];
+} vk_mg_scene;
+#define VK_MG_SCENES_DEV_BYTES(n) ((size_t)(n) * sizeof(vk_mg_scene))
+size_t vk_mg_scenes_dev_bytes(int n);
+int vk_mg_render(int n, int S, const vk_mg_scene* scenes_host, void* scenes_dev, size_t scenes_dev_bytes, uint8_t* rgb, uint8_t* mask,
+                 void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Distance maps of masks: the exact squared Euclidean distance transform, the signed map of the boundary loss

@@ -10,12 +10,13 @@ Import by string (the directory name carries hyphens)::
     optimizer = vk.adamw_for(model, lr=5e-5, weight_decay=1e-4)
 
 Everything heavy runs in libvkunet.so (hand-written HIP); there is no CPU fallback."""
-from . import _lib, augment, averaging, boundary, copypaste, encoders, geometry, inputs, instances, losses, lovasz, multiclass, parallel, patches, prepost, render, seglosses, segmetrics, subpix, sweep, synthetic, tiling, zoom  # noqa: F401
+from . import _lib, augment, averaging, boundary, copypaste, encoders, geometry, inputs, instances, losses, lovasz, micrographs, multiclass, parallel, patches, prepost, render, seglosses, segmetrics, subpix, sweep, synthetic, tiling, zoom  # noqa: F401
 from .augment import AugmentSampler, DeviceDataset  # noqa: F401
 from .averaging import SWA, ModelEMA  # noqa: F401
 from .patches import PatchDataset, PatchSampler  # noqa: F401
 from .copypaste import CopyPaste, CopyPasteSampler, InstanceBank  # noqa: F401
 from .boundary import BoundaryLoss, BoundaryMetrics  # noqa: F401
+from .micrographs import MicrographDataset, SceneSampler  # noqa: F401
 from .geometry import (postprocess_minarearect_batch, postprocess_minarearect_multi, postprocess_quadrilateral_batch,  # noqa: F401
                        postprocess_quadrilateral_multi)
 from ._lib import VkError, build, lib  # noqa: F401
@@ -43,4 +44,5 @@ __all__ = ["Unet", "build_model", "DiceLoss", "BCEDiceLoss", "multiclass", "enco
            "averaging", "ModelEMA", "SWA",
            "copypaste", "InstanceBank", "CopyPasteSampler", "CopyPaste",
            "boundary", "BoundaryLoss", "BoundaryMetrics",
-           "inputs"]
+           "inputs",
+           "micrographs", "SceneSampler", "MicrographDataset"]

@@ -98,6 +98,38 @@ def vk_cp_recs_dev_bytes(n: int) -> int:
     return n * (VK_CP_MAX_PASTES * C.sizeof(vk_cp_rec) + 4)
 
 
+VK_MG_MAX_INDENTS, VK_MG_MAX_SCRATCHES, VK_MG_MAX_BLOBS, VK_MG_MAX_RECTS = 8, 64, 8, 4
+VK_MG_MIN_SIDE, VK_MG_MAX_SIDE, VK_MG_COORD_MARGIN = 16, 1024, 8192
+
+
+class vk_mg_indent(C.Structure):
+    _fields_ = [("vx", C.c_int32 * 4), ("vy", C.c_int32 * 4), ("ax", C.c_int32), ("ay", C.c_int32), ("shade", C.c_int32 * 4),
+                ("slope", C.c_int32 * 4), ("ridge", C.c_int32), ("ridge_hw", C.c_int32), ("halo_r", C.c_int32), ("halo_depth", C.c_int32),
+                ("reserved", C.c_int32 * 2)]
+
+
+class vk_mg_scratch(C.Structure):
+    _fields_ = [(f, C.c_int32) for f in ("x", "y", "dx", "dy", "hw", "depth", "t0", "t1")]
+
+
+class vk_mg_blob(C.Structure):
+    _fields_ = [(f, C.c_int32) for f in ("x", "y", "r", "dark")]
+
+
+class vk_mg_rect(C.Structure):
+    _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32), ("thickness", C.c_int32), ("color", C.c_int32 * 3)]
+
+
+class vk_mg_scene(C.Structure):
+    _fields_ = [("n_indents", C.c_int32), ("n_scratches", C.c_int32), ("n_blobs", C.c_int32), ("n_rects", C.c_int32), ("base", C.c_int32),
+                ("tint", C.c_int32 * 3), ("grad_x", C.c_int32), ("grad_y", C.c_int32), ("grad_cx", C.c_int32), ("grad_cy", C.c_int32),
+                ("vig_cx", C.c_int32), ("vig_cy", C.c_int32), ("vig", C.c_int32), ("tex_amp", C.c_int32), ("tex_cos", C.c_int32),
+                ("tex_sin", C.c_int32), ("tex_lu", C.c_int32), ("tex_lv", C.c_int32), ("tex_seed", C.c_uint32), ("blur_r", C.c_int32),
+                ("noise_amp", C.c_int32), ("noise_seed", C.c_uint32), ("reserved", C.c_int32 * 8),
+                ("indents", vk_mg_indent * VK_MG_MAX_INDENTS), ("scratches", vk_mg_scratch * VK_MG_MAX_SCRATCHES),
+                ("blobs", vk_mg_blob * VK_MG_MAX_BLOBS), ("rects", vk_mg_rect * VK_MG_MAX_RECTS)]
+
+
 VK_EDT_MAX_SIDE, VK_EDT_NONE = 4096, 0x7FFFFFFF
 VK_EDT_FG, VK_EDT_BG, VK_EDT_EDGE, VK_EDT_ROWS_ENVELOPE, VK_EDT_ROWS_SEARCH = 0, 1, 2, 0x100, 0x200
 VK_EDT_SRC_U8, VK_EDT_SRC_F32 = 0, 1
@@ -291,6 +323,8 @@ SIGNATURES = {
     "vk_cp_boxes": (ci, [ci, ci, ci, vp, ci, vp, vp]),
     "vk_cp_alpha": (ci, [ci, ci, ci, vp, vp, vp, vp]),
     "vk_cp_paste": (ci, [ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "vk_mg_scenes_dev_bytes": (sz, [ci]),
+    "vk_mg_render": (ci, [ci, ci, vp, vp, sz, vp, vp, vp]),
     "vk_edt_workspace_bytes": (sz, [ci, ci, ci]),
     "vk_edt_sq": (ci, [ci, ci, ci, vp, ci, cf, ci, vp, vp, sz, vp]),
     "vk_boundary_phi": (ci, [ci, ci, ci, vp, vp, vp, vp]),

@@ -1149,6 +1149,88 @@ int vk_subpix_refine(const vk_subpix_params* params, int batch, int h, int w, co
                      size_t record_stride, size_t box_offset, int valid_offset, const int32_t* counts, int max_components,
                      const double* affine, vk_subpix_quad* out, void* stream);
 
+/* Vertex heatmaps (keypoints.hip): the targets of a heatmap plane beside the mask, and its read-out.
+ *
+ * Conventions of the three calls.  Coordinates are those of the geometry records: pixel (x, y) lies at the point (x, y).  Records are
+ * read in place as vk_subpix_refine reads them: slot t of map b is at (char*)records + ((size_t)b * max_components + t) * record_stride,
+ * and the slots used are t < min(max(counts[b], 0), max_components) with valid != 0 (valid_offset -1: every slot is valid).  A map of
+ * image b begins at base + b * image_stride (in elements, at least h * w) and its rows are w elements apart, so plane 1 of a
+ * [N][2][h][w] tensor is written or read in place with image_stride = 2 h w.  batch 1..65535, h, w >= 1 with h * w <= 2^30,
+ * max_components 1..4096.  No transcendental runs on the device and there is no float atomic; float64 where stated, contraction off,
+ * every expression evaluated as written.  Every call checks its arguments on the host and returns VK_ERR_ARG before anything touches
+ * the stream.
+ *
+ * vk_kp_targets: vertex records -> a heatmap.  vert_type VK_KP_VERT_I32 reads int32[8] at vert_offset (box of vk_geom_det and
+ * vk_geom_quad; offset and stride multiples of 4): X = 16 * x in int64.  VK_KP_VERT_F64 reads double[8] (v of vk_subpix_quad, or a
+ * bare [batch][max_components][8] array with record_stride 64, vert_offset 0 and valid_offset -1; offset and stride multiples of 8,
+ * records 8-byte aligned): a vertex is skipped unless fabs(v) <= 2^20 for both coordinates (a NaN fails), else
+ * X = (int64)floor(v * 16.0 + 0.5); Y likewise.  table: device float32 [table_len], table_len = R16 * R16 + 1 with
+ * 1 <= R16 <= VK_KP_MAX_RADIUS16; the caller builds it (table[k] = float32(exp(-(k / 256) / (2 sigma^2))) for a Gaussian of sigma
+ * pixels).  For output pixel (x, y) and every used vertex in ascending (slot, q): D = (16 x - X)^2 + (16 y - Y)^2, exact (a vertex
+ * further than R16 in either axis has D >= table_len whatever its size); if D < table_len: v = table[D], if (v > best) best = v.
+ * best starts at 0.0f, so a NaN never wins; out[b][y][x] = best.  Every element of the batch planes is written exactly once and
+ * nothing else is.  flags: 0 (the library's choice), VK_KP_TABLE_MEMORY or VK_KP_TABLE_LDS (table_len <= VK_KP_TABLE_LDS_MAX): where
+ * the table is read from; the bytes written are the same.  out is 4-byte aligned; a 16-byte aligned out with image_stride and w
+ * multiples of 4 takes the 16-byte store path, with the same bytes.
+ *
+ * vk_kp_peaks: a heatmap -> the list of its local maxima.  Pixel (x, y) of value p is a peak iff (double)p >= min_peak (finite), no
+ * pixel of the (2 r + 1)^2 window around it inside the map has p' > p, and no raster-earlier pixel of that window has p' == p;
+ * r = nms_radius, 1..VK_KP_MAX_NMS.  A NaN is never a peak and never suppresses one.  out: vk_kp_peak records
+ * [batch][max_peaks] (max_peaks 1..4096) in raster order, the first max_peaks of each map; counts[b] = the number of all peaks, also
+ * above max_peaks; slots at or above min(counts[b], max_peaks) are not touched.  A count pass, an ordered prefix and an emit pass: no
+ * atomics.  workspace: vk_kp_peaks_workspace_bytes (0 for arguments out of range) = VK_KP_PEAKS_WS_BYTES, 4-byte aligned; it need
+ * not be cleared.
+ *
+ * vk_kp_refine: first-pass records and a heatmap -> vk_subpix_quad records.  The arguments of vk_subpix_refine with heat and its
+ * image_stride in place of prob.  search 1..VK_KP_MAX_SEARCH, cwin 1..VK_KP_MAX_CWIN, min_peak finite, floor_frac in [0, 1).  Per
+ * vertex, s = the int32 corner.  Peak: the largest value of the (2 search + 1)^2 window around s clipped to the map, the raster-first
+ * pixel among equal values; a NaN never wins.  No pixel in the window (or only NaNs), or (double)peak < min_peak: flag VK_KP_NO_PEAK,
+ * the vertex keeps s.  A peak on the border of the unclipped window: flag VK_KP_AT_EDGE, the estimate is kept.  With the peak at
+ * (px, py) of value c:
+ *   VK_KP_PARABOLA, per axis in float64 on the float32 values l, c, r of the peak's row (column): den = (l - c) + (r - c); the offset
+ *     is 0.5 * (l - r) / den when den < 0 and the peak is not on the map's border in that axis, else 0; q = (px + ox, py + oy).
+ *   VK_KP_CENTROID: fl = floor_frac * c; over the (2 cwin + 1)^2 window around the peak clipped to the map, j ascending then i
+ *     ascending, from 0.0: g = p - fl if that is above 0, else 0 (a NaN gives 0); sw += g, sx += g * (i - px), sy += g * (j - py);
+ *     q = (px + sx / sw, py + sy / sw) when sw > 0, else (px, py).
+ * A map that holds an infinity can give a NaN estimate (inf - inf), whose sign bit is the hardware's; NaNs and finite values give the
+ * same bytes everywhere.
+ * After the four vertices: any two that used the same peak pixel both get VK_KP_SHARED and keep s.  iters[q] is 1 where a peak was
+ * used, else 0.  label, area, valid, v, vs, d1, d2, d_mean and the record of valid == 0 are those of vk_subpix_refine. */
+#define VK_KP_VERT_I32 0
+#define VK_KP_VERT_F64 1
+#define VK_KP_MAX_RADIUS16 192
+#define VK_KP_MAX_NMS 8
+#define VK_KP_MAX_SEARCH 31
+#define VK_KP_MAX_CWIN 7
+#define VK_KP_TABLE_MEMORY 1
+#define VK_KP_TABLE_LDS 2
+#define VK_KP_TABLE_LDS_MAX 15360
+#define VK_KP_PARABOLA 0
+#define VK_KP_CENTROID 1
+#define VK_KP_NO_PEAK 128     /* beside the VK_SUBPIX_* bits, in the same flags field */
+#define VK_KP_AT_EDGE 256
+#define VK_KP_SHARED 512
+#define VK_KP_PEAKS_WS_BYTES(batch, h, w) ((size_t)(batch) * (((size_t)(h) * (size_t)(w) + 1023) / 1024) * 260)
+typedef struct vk_kp_peak {
+  int32_t x, y;
+  float value;
+  int32_t reserved;             /* written as 0 */
+} vk_kp_peak;
+typedef struct vk_kp_params {
+  int method;                   /* VK_KP_PARABOLA / VK_KP_CENTROID */
+  int search, cwin;
+  double min_peak, floor_frac;
+} vk_kp_params;
+int vk_kp_targets(int batch, int h, int w, const void* records, size_t record_stride, size_t vert_offset, int vert_type,
+                  int valid_offset, const int32_t* counts, int max_components, const float* table, int table_len, float* out,
+                  size_t image_stride, int flags, void* stream);
+size_t vk_kp_peaks_workspace_bytes(int batch, int h, int w);
+int vk_kp_peaks(int batch, int h, int w, const float* heat, size_t image_stride, double min_peak, int nms_radius, int max_peaks,
+                vk_kp_peak* out, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+int vk_kp_refine(const vk_kp_params* params, int batch, int h, int w, const float* heat, size_t image_stride, const void* records,
+                 size_t record_stride, size_t box_offset, int valid_offset, const int32_t* counts, int max_components,
+                 const double* affine, vk_subpix_quad* out, void* stream);
+
 /* Second-pass inference on one window per indentation (zoom.hip).  The first pass detects on the letterboxed
  * map; for every detection one S x S window is cut from the uint8 source image at the finest scale that still shows the indentation
  * whole, the caller segments, fits and refines there (vk_geom_*, vk_subpix_refine with the window's affine row), and vk_zoom_merge

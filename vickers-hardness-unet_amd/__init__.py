@@ -10,7 +10,7 @@ Import by string (the directory name carries hyphens)::
     optimizer = vk.adamw_for(model, lr=5e-5, weight_decay=1e-4)
 
 Everything heavy runs in libvkunet.so (hand-written HIP); there is no CPU fallback."""
-from . import _lib, augment, averaging, boundary, copypaste, encoders, geometry, inputs, instances, losses, lovasz, micrographs, multiclass, parallel, patches, prepost, render, seglosses, segmetrics, subpix, sweep, synthetic, tiling, zoom  # noqa: F401
+from . import _lib, augment, averaging, boundary, copypaste, encoders, geometry, inputs, instances, keypoints, losses, lovasz, micrographs, multiclass, parallel, patches, prepost, render, seglosses, segmetrics, subpix, sweep, synthetic, tiling, zoom  # noqa: F401
 from .augment import AugmentSampler, DeviceDataset  # noqa: F401
 from .averaging import SWA, ModelEMA  # noqa: F401
 from .patches import PatchDataset, PatchSampler  # noqa: F401
@@ -45,4 +45,5 @@ __all__ = ["Unet", "build_model", "DiceLoss", "BCEDiceLoss", "multiclass", "enco
            "copypaste", "InstanceBank", "CopyPasteSampler", "CopyPaste",
            "boundary", "BoundaryLoss", "BoundaryMetrics",
            "inputs",
-           "micrographs", "SceneSampler", "MicrographDataset"]
+           "micrographs", "SceneSampler", "MicrographDataset",
+           "keypoints"]

@@ -195,6 +195,21 @@ class vk_subpix_quad(C.Structure):
                 ("d_mean", C.c_double)]
 
 
+VK_KP_VERT_I32, VK_KP_VERT_F64 = 0, 1
+VK_KP_MAX_RADIUS16, VK_KP_MAX_NMS, VK_KP_MAX_SEARCH, VK_KP_MAX_CWIN = 192, 8, 31, 7
+VK_KP_TABLE_MEMORY, VK_KP_TABLE_LDS, VK_KP_TABLE_LDS_MAX = 1, 2, 15360
+VK_KP_PARABOLA, VK_KP_CENTROID = 0, 1
+KP_FLAGS = {"no_peak": 128, "at_edge": 256, "shared": 512}
+
+
+class vk_kp_peak(C.Structure):
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("value", C.c_float), ("reserved", C.c_int32)]
+
+
+class vk_kp_params(C.Structure):
+    _fields_ = [("method", C.c_int), ("search", C.c_int), ("cwin", C.c_int), ("min_peak", C.c_double), ("floor_frac", C.c_double)]
+
+
 ZOOM_STATUS = {"clipped": 1, "scale_clamped_lo": 2, "scale_clamped_hi": 4, "zoomed": 16, "no_target": 32, "refine_failed": 64,
                "disagrees": 128, "no_window": 256}
 VK_ZOOM_FAIL_MASK = 0x7F
@@ -374,6 +389,10 @@ SIGNATURES = {
     "vk_inst_contingency": (ci, [ci, ci, ci, vp, vp, ci, ci, vp, vp]),
     "vk_inst_match": (ci, [ci, ci, ci, vp, vp, vp, ci, vp, vp, sz, vp, sz, vp, vp, vp, vp, vp, ci, vp]),
     "vk_subpix_refine": (ci, [P(vk_subpix_params), ci, ci, ci, vp, vp, sz, sz, ci, vp, ci, vp, vp, vp]),
+    "vk_kp_targets": (ci, [ci, ci, ci, vp, sz, sz, ci, ci, vp, ci, vp, ci, vp, sz, ci, vp]),
+    "vk_kp_peaks_workspace_bytes": (sz, [ci, ci, ci]),
+    "vk_kp_peaks": (ci, [ci, ci, ci, vp, sz, cd, ci, ci, vp, vp, vp, sz, vp]),
+    "vk_kp_refine": (ci, [P(vk_kp_params), ci, ci, ci, vp, sz, vp, sz, sz, ci, vp, ci, vp, vp, vp]),
     "vk_zoom_windows": (ci, [P(vk_zoom_params), ci, vp, sz, sz, ci, vp, ci, vp, vp, vp, vp, vp]),
     "vk_zoom_gather": (ci, [ci, ci, vp, ci, P(vk_zoom_image), vp, ci, ci, vp, vp]),
     "vk_zoom_merge": (ci, [ci, cd, ci, vp, vp, sz, sz, ci, vp, ci, vp, ci, ci, vp, vp, vp, vp, vp, vp]),

@@ -15,6 +15,7 @@
 // and mirrored line for line by tests/subpix_ref.py.  Every index is formed from a clamped coordinate: nothing read from the map or
 // from a record can address memory outside the map.
 #include "vk_common.h"
+#include "subpix_tail.h"
 
 #include <float.h>
 #include <math.h>
@@ -262,17 +263,7 @@ __global__ __launch_bounds__(256) void k_subpix(const vk_subpix_params P, int h,
   const int valid = valid_off >= 0 ? (*reinterpret_cast<const int*>(rec + valid_off) != 0 ? 1 : 0) : 1;
   vk_subpix_quad* dst = out + (size_t)b * M + slot;
   if (!valid) {                                                // the whole workgroup again
-    if (tid == 0) {
-      dst->label = reinterpret_cast<const int*>(rec)[0];
-      dst->area = reinterpret_cast<const int*>(rec)[1];
-      dst->valid = 0;
-      dst->reserved = 0;
-      for (int q = 0; q < 4; ++q) { dst->flags[q] = 0; dst->iters[q] = 0; }
-      for (int q = 0; q < 8; ++q) { dst->v[q] = 0.0; dst->vs[q] = 0.0; }
-      dst->d1 = 0.0;
-      dst->d2 = 0.0;
-      dst->d_mean = 0.0;
-    }
+    if (tid == 0) sp_write_invalid(dst, rec);
     return;
   }
   const float* map = prob + (size_t)b * ((size_t)h * w);
@@ -284,38 +275,7 @@ __global__ __launch_bounds__(256) void k_subpix(const vk_subpix_params P, int h,
   if (lane == 0) { s_vx[wave] = r.x; s_vy[wave] = r.y; s_fl[wave] = r.flags; s_it[wave] = r.iters; }
   __syncthreads();
   if (tid != 0) return;
-  double ox = 0.0, oy = 0.0, inv = 1.0;
-  if (affine) { ox = affine[3 * (size_t)b]; oy = affine[3 * (size_t)b + 1]; inv = affine[3 * (size_t)b + 2]; }
-  dst->label = reinterpret_cast<const int*>(rec)[0];
-  dst->area = reinterpret_cast<const int*>(rec)[1];
-  dst->valid = 1;
-  dst->reserved = 0;
-  for (int q = 0; q < 4; ++q) {
-    dst->flags[q] = s_fl[q];
-    dst->iters[q] = s_it[q];
-    dst->v[2 * q] = s_vx[q];
-    dst->v[2 * q + 1] = s_vy[q];
-    dst->vs[2 * q] = (s_vx[q] - ox) * inv;
-    dst->vs[2 * q + 1] = (s_vy[q] - oy) * inv;
-  }
-  // the geometry records' rule: the longest of the six pairs (the first on a tie), then the other two vertices
-  double dmax = -1.0;
-  int i1 = 0, j1 = 1;
-  for (int a = 0; a < 4; ++a)
-    for (int c = a + 1; c < 4; ++c) {
-      const double ddx = s_vx[a] - s_vx[c], ddy = s_vy[a] - s_vy[c];
-      const double d = sqrt(ddx * ddx + ddy * ddy);
-      if (d > dmax) { dmax = d; i1 = a; j1 = c; }
-    }
-  int r0 = -1, r1 = -1;
-  for (int q = 0; q < 4; ++q)
-    if (q != i1 && q != j1) { if (r0 < 0) r0 = q; else r1 = q; }
-  const double ex = s_vx[r0] - s_vx[r1], ey = s_vy[r0] - s_vy[r1];
-  const double d1 = dmax * inv;
-  const double d2 = sqrt(ex * ex + ey * ey) * inv;
-  dst->d1 = d1;
-  dst->d2 = d2;
-  dst->d_mean = 0.5 * (d1 + d2);
+  sp_write_record(dst, rec, affine, b, s_vx, s_vy, s_fl, s_it);             // subpix_tail.h: shared with vk_kp_refine
 }
 
 }  // namespace vk

@@ -1231,6 +1231,44 @@ int vk_kp_refine(const vk_kp_params* params, int batch, int h, int w, const floa
                  size_t record_stride, size_t box_offset, int valid_offset, const int32_t* counts, int max_components,
                  const double* affine, vk_subpix_quad* out, void* stream);
 
+/* ---- per-plane pixel losses of a keypoint head (kp_loss.hip).  logits fp32 [N][C][HW], target fp32 [N][C][HW]
+ * with values in [0, 1] (the y2 of vk.keypoints.make_targets), 1 <= C <= 16.  Every plane follows one of three rules, given as two
+ * disjoint bit masks that are not both empty and name no plane >= C; with e = expf(-|x|), l1p = log1pf(e), p = sigmoid(x) and
+ * omp = 1 - p as vk_seg_loss forms them, log p = -(max(-x, 0) + l1p), log(1 - p) = -(max(x, 0) + l1p):
+ *   heat plane c  (penalty-reduced focal loss; alpha, beta integers in 0..VK_KP_LOSS_MAX_EXP): an entry is positive iff
+ *            y >= pos_threshold;  positive: -omp^alpha log p;  negative: -(1 - y)^beta p^alpha log(1 - p);
+ *            S_c = the sum over (N, HW), P_c = the number of positives, plane value = S_c / max(P_c, 1);  heat = mean over the heat
+ *            planes.  Powers are left-to-right fp32 products (q^0 = 1, q^1 = q, q^2 = q q, q^3 = (q q) q, ...).
+ *            d/dx positive: alpha p omp^alpha log p - omp^(alpha + 1);  negative: (1 - y)^beta (p^(alpha + 1) - alpha p^alpha omp log(1 - p))
+ *   BCE plane c   torch BCEWithLogitsLoss(pos_weight): max(x, 0) - x y + l1p + (pw_c - 1) y softplus(-x) per entry, the mean over all
+ *            N HW (number of BCE planes) entries;  d/dx = p - y - (pw_c - 1) y omp  (the pixel term of vk_seg_loss at pix_smooth 0)
+ *   neither       the plane is not read
+ * total = w_heat heat + w_bce bce.  Up to four fp32 element values are added, then accumulated in fp64; per-workgroup partial rows are
+ * added in a fixed order; positives are counted in integers; no float atomics: the same inputs give the same bytes.  16-byte accesses
+ * when HW % 4 == 0 and the buffers are 16-byte aligned.  Targets outside [0, 1] are the caller's error (not checked); a NaN propagates.
+ * struct_size must be the size of the structure. */
+#define VK_KP_LOSS_MAX_EXP 8
+typedef struct vk_kp_loss_cfg {
+  uint32_t struct_size;
+  uint32_t heat_planes, bce_planes;
+  float w_heat, w_bce;
+  int32_t alpha, beta;
+  float pos_threshold;              /* in (0, 1] */
+  int32_t has_pos_weight;
+  float pos_weight[16];
+} vk_kp_loss_cfg;
+size_t vk_kp_loss_cfg_size(void);
+/* Device scratch (8-byte aligned; the caller owns it); 0 for arguments out of range: N, HW >= 1, HW <= 2^28, N C <= 65535,
+ * N C HW <= 2^31 - 1. */
+size_t vk_kp_loss_workspace_bytes(int N, int C, int HW);
+/* loss_out float[8] = {total, heat, bce, 0, ...}; positives (optional) int64[16]: P_c of the heat planes, 0 elsewhere; dlogits
+ * (optional) = grad_scale * d total / dx: accumulate = 0 writes every entry (planes with neither rule get 0), accumulate = 1 adds
+ * into the planes that have a rule and leaves the others untouched.  Every argument error is found on the host before any launch
+ * (VK_ERR_ARG and vk_last_error_string). */
+int vk_kp_loss(const vk_kp_loss_cfg* cfg, int N, int C, int HW, const float* logits, const float* target, void* workspace,
+               size_t workspace_bytes, float* loss_out, int64_t* positives, float* dlogits, float grad_scale, int accumulate,
+               void* stream);
+
 /* Second-pass inference on one window per indentation (zoom.hip).  The first pass detects on the letterboxed
  * map; for every detection one S x S window is cut from the uint8 source image at the finest scale that still shows the indentation
  * whole, the caller segments, fits and refines there (vk_geom_*, vk_subpix_refine with the window's affine row), and vk_zoom_merge
@@ -1640,6 +1678,13 @@ int vk_unet_loss_cfg(vk_unet* h, const vk_seg_loss_cfg* cfg, const void* logits,
  * labels include the Lovasz part), [8] the Lovasz value, [9] its bad labels. */
 int vk_unet_loss_lovasz(vk_unet* h, const vk_seg_loss_cfg* seg_cfg, const vk_lovasz_cfg* lovasz_cfg, float w_lovasz, const void* logits,
                         const void* target, void* workspace, size_t workspace_bytes, float* loss_out, float grad_scale, void* stream);
+/* The fused step with per-plane keypoint losses: vk_unet_loss_lovasz with the second part exchanged.  Runs vk_seg_loss on seg_cfg
+ * (binary or multilabel; NULL: no such part, the first 8 floats are cleared), then vk_kp_loss adding into (or, without a seg part,
+ * writing) the plan's dlogits.  workspace: of vk_kp_loss_workspace_bytes(N, classes, S S), the caller's.  loss_out float[16]: [0, 8)
+ * as vk_seg_loss with the kp total added to [0], [8] heat, [9] bce, [10] the kp total.  Both configurations are checked before any
+ * launch. */
+int vk_unet_loss_kp(vk_unet* h, const vk_seg_loss_cfg* seg_cfg, const vk_kp_loss_cfg* kp_cfg, const void* logits, const void* target,
+                    void* workspace, size_t workspace_bytes, float* loss_out, float grad_scale, void* stream);
 /* dlogits: fp32 [N][C][S][S] gradient of the loss wrt the logits, or NULL to use the one vk_unet_loss
  * left in the workspace.  Runs backward stages [stage_begin, stage_end); stage i completes gradient bucket i.  Gradients are
  * accumulated into the flat grad buffer (caller zeroes it once per step, e.g. via vk_unet_zero_grad).

@@ -210,6 +210,15 @@ class vk_kp_params(C.Structure):
     _fields_ = [("method", C.c_int), ("search", C.c_int), ("cwin", C.c_int), ("min_peak", C.c_double), ("floor_frac", C.c_double)]
 
 
+VK_KP_LOSS_MAX_EXP = 8
+
+
+class vk_kp_loss_cfg(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("heat_planes", C.c_uint32), ("bce_planes", C.c_uint32), ("w_heat", C.c_float),
+                ("w_bce", C.c_float), ("alpha", C.c_int32), ("beta", C.c_int32), ("pos_threshold", C.c_float),
+                ("has_pos_weight", C.c_int32), ("pos_weight", C.c_float * 16)]
+
+
 ZOOM_STATUS = {"clipped": 1, "scale_clamped_lo": 2, "scale_clamped_hi": 4, "zoomed": 16, "no_target": 32, "refine_failed": 64,
                "disagrees": 128, "no_window": 256}
 VK_ZOOM_FAIL_MASK = 0x7F
@@ -393,6 +402,9 @@ SIGNATURES = {
     "vk_kp_peaks_workspace_bytes": (sz, [ci, ci, ci]),
     "vk_kp_peaks": (ci, [ci, ci, ci, vp, sz, cd, ci, ci, vp, vp, vp, sz, vp]),
     "vk_kp_refine": (ci, [P(vk_kp_params), ci, ci, ci, vp, sz, vp, sz, sz, ci, vp, ci, vp, vp, vp]),
+    "vk_kp_loss_cfg_size": (sz, []),
+    "vk_kp_loss_workspace_bytes": (sz, [ci, ci, ci]),
+    "vk_kp_loss": (ci, [P(vk_kp_loss_cfg), ci, ci, ci, vp, vp, vp, sz, vp, vp, vp, cf, ci, vp]),
     "vk_zoom_windows": (ci, [P(vk_zoom_params), ci, vp, sz, sz, ci, vp, ci, vp, vp, vp, vp, vp]),
     "vk_zoom_gather": (ci, [ci, ci, vp, ci, P(vk_zoom_image), vp, ci, ci, vp, vp]),
     "vk_zoom_merge": (ci, [ci, cd, ci, vp, vp, sz, sz, ci, vp, ci, vp, ci, ci, vp, vp, vp, vp, vp, vp]),
@@ -436,6 +448,7 @@ SIGNATURES = {
     "vk_unet_loss_ex": (ci, [vp, ci, vp, vp, vp, cf, cf, cf, vp]),
     "vk_unet_loss_cfg": (ci, [vp, P(vk_seg_loss_cfg), vp, vp, vp, cf, vp]),
     "vk_unet_loss_lovasz": (ci, [vp, P(vk_seg_loss_cfg), P(vk_lovasz_cfg), cf, vp, vp, vp, sz, vp, cf, vp]),
+    "vk_unet_loss_kp": (ci, [vp, P(vk_seg_loss_cfg), P(vk_kp_loss_cfg), vp, vp, vp, sz, vp, cf, vp]),
     "vk_unet_backward": (ci, [vp, vp, ci, ci, vp]),
     "vk_unet_set_trainable": (ci, [vp, P(C.c_uint8), ci]),
     "vk_unet_set_bn_frozen": (ci, [vp, P(C.c_uint8), ci]),

@@ -1352,6 +1352,27 @@ extern "C" int vk_unet_loss_lovasz(vk_unet* h, const vk_seg_loss_cfg* seg_cfg, c
   return vk::lovasz_combine(loss_out, w_lovasz, st);
 }
 
+extern "C" int vk_unet_loss_kp(vk_unet* h, const vk_seg_loss_cfg* seg_cfg, const vk_kp_loss_cfg* kp_cfg, const void* logits,
+                               const void* target, void* workspace, size_t workspace_bytes, float* loss_out, float grad_scale,
+                               void* stream) {
+  VK_CHECK_ARG(h && h->bound && kp_cfg && logits && target && workspace && loss_out, "vk_unet_loss_kp: plan not bound or null argument");
+  VK_CHECK_ARG(!seg_cfg || seg_cfg->mode == VK_LOSS_BINARY || seg_cfg->mode == VK_LOSS_MULTILABEL,
+               "vk_unet_loss_kp: the vk_seg_loss part must be binary or multilabel");
+  VK_CHECK_ARG(grad_scale == grad_scale && grad_scale - grad_scale == 0.f, "vk_unet_loss_kp: grad_scale is not finite");
+  const int N = h->cfg.N, HW = h->cfg.size * h->cfg.width;
+  if (!vk::kp_check(kp_cfg, N, h->classes, HW, "vk_unet_loss_kp") ||
+      !vk::kp_check_workspace(N, h->classes, HW, workspace, workspace_bytes, "vk_unet_loss_kp"))
+    return VK_ERR_ARG;
+  float* dl = h->cfg.training ? (float*)(h->ws + h->off_dlogits) : nullptr;
+  hipStream_t st = (hipStream_t)stream;
+  if (seg_cfg) RET_IF(vk_seg_loss(seg_cfg, N, h->classes, HW, (const float*)logits, target, h->ws + h->off_sloss, h->sloss_bytes, loss_out,
+                                  dl, grad_scale, stream));
+  else VK_CHECK_HIP(hipMemsetAsync(loss_out, 0, 8 * sizeof(float), st));
+  RET_IF(vk_kp_loss(kp_cfg, N, h->classes, HW, (const float*)logits, (const float*)target, workspace, workspace_bytes, loss_out + 8,
+                    nullptr, dl, grad_scale, seg_cfg ? 1 : 0, stream));
+  return vk::kp_combine(loss_out, st);
+}
+
 extern "C" int vk_unet_loss(vk_unet* h, const float* logits, const float* target, float* loss_out, float grad_scale, float w_bce,
                             float w_dice, void* stream) {
   VK_CHECK_ARG(h && h->bound && logits && target && loss_out, "vk_unet_loss: plan not bound or null tensor");

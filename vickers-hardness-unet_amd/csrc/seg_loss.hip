@@ -14,6 +14,7 @@
 // 16-byte aligned; otherwise the same code runs with one pixel per thread.
 #include <math.h>
 
+#include "sl_sigmoid.h"      // SlSig, sl_sigmoid: shared with kp_loss.hip
 #include "vk_common.h"
 
 namespace vk {
@@ -45,20 +46,6 @@ __device__ __forceinline__ void sl_pow(float q, float gamma, int gmode, float* q
     *qg = __builtin_amdgcn_exp2f(gamma * lq);
     *dqg = gamma * __builtin_amdgcn_exp2f((gamma - 1.f) * lq);
   }
-}
-
-// sigmoid pieces of one logit without overflow: e = exp(-|x|), l1p = log1p(e), p = sigmoid(x), omp = 1 - p
-struct SlSig {
-  float e, l1p, p, omp;
-};
-__device__ __forceinline__ SlSig sl_sigmoid(float x) {
-  SlSig s;
-  s.e = expf(-fabsf(x));
-  s.l1p = log1pf(s.e);
-  const float r = 1.f / (1.f + s.e);
-  s.p = x >= 0.f ? r : s.e * r;
-  s.omp = x >= 0.f ? s.e * r : r;
-  return s;
 }
 
 // focal term of one logit against y: value (1 - e^-b)^gamma b aw and its derivative, b = BCE-with-logits(x, y)

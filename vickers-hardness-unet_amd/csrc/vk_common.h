@@ -345,4 +345,9 @@ int wgrad_batch_build(const vk_conv_desc* descs, const void* const* dz, float* c
 int wgrad_batch_launch(vk_dtype dt, const WgradBatchPlan& plan, const void* tables, void* slab, size_t slab_bytes, hipStream_t st);
 // lovasz.hip (used by engine.hip): loss_out[0] += w * loss_out[8], loss_out[6] += loss_out[9]
 int lovasz_combine(float* loss_out, float w, hipStream_t st);
+// kp_loss.hip (used by engine.hip): the host-side checks of vk_kp_loss (false: the text is set), and
+// loss_out[0] += kp total, loss_out[8, 11) = {heat, bce, kp total}
+bool kp_check(const vk_kp_loss_cfg* cfg, int N, int C, int HW, const char* who);
+bool kp_check_workspace(int N, int C, int HW, const void* workspace, size_t workspace_bytes, const char* who);
+int kp_combine(float* loss_out, hipStream_t st);
 }  // namespace vk

@@ -177,7 +177,11 @@ class ObjectMetrics:
     ``update`` synchronises with nothing; ``compute`` reads the totals back once.  ``pred_args`` go to ``detect`` for the prediction;
     the target is detected with the ground-truth preset.  ``refine``: None, or a dict of ``vk.subpix.refine`` arguments (``method``,
     ``affine``, its parameters): then the corners of both the prediction's and the target's records are refined below a pixel before
-    the diagonals are compared."""
+    the diagonals are compared.  ``refine=dict(kind="keypoints", sigma=..., **refine_args)``: the vertex heatmap read-out instead;
+    ``update`` then takes the predicted heatmap as ``heat``, the prediction's records go through ``vk.keypoints.refine(pred, heat,
+    **refine_args)`` and the target's through the same call on the exact heatmap of their own integer corners
+    (``vk.keypoints.targets(gt, shape, sigma)``), which returns those corners as ``RefinedDetections``.  ``kind="subpix"`` or no
+    ``kind`` is ``vk.subpix.refine``."""
 
     def __init__(self, fit: str = "rect", iou_thresholds=None, max_components: int = 64, fit_outset_px: int = G.FIT_OUTSET_PX,
                  refine: Optional[dict] = None, **pred_args):
@@ -188,6 +192,17 @@ class ObjectMetrics:
             raise ValueError("refine must be None or a dict of vk.subpix.refine arguments, got %r" % (refine,))
         self.thresholds = _iou_thresholds(iou_thresholds)
         self.refine = None if refine is None else dict(refine)
+        self.refine_kind, self.kp_sigma = "subpix", None
+        if self.refine is not None and "kind" in self.refine:
+            self.refine_kind = self.refine.pop("kind")
+            if self.refine_kind not in ("subpix", "keypoints"):
+                raise ValueError("refine kind must be 'subpix' or 'keypoints', got %r" % (self.refine_kind,))
+            if self.refine_kind == "keypoints":
+                if "sigma" not in self.refine:
+                    raise ValueError("refine=dict(kind='keypoints') needs sigma, the width of the heatmap's bumps in pixels")
+                self.kp_sigma = float(self.refine.pop("sigma"))
+                if not (self.kp_sigma > 0.0 and self.kp_sigma < float("inf")):
+                    raise ValueError("refine sigma must be positive and finite, got %r" % (self.kp_sigma,))
         self.fit, self.max_components, self.fit_outset_px, self.pred_args = fit, int(max_components), int(fit_outset_px), dict(pred_args)
         self.reset()
 
@@ -198,14 +213,25 @@ class ObjectMetrics:
     def n_images(self) -> int:
         return self._images
 
-    def update(self, prob: torch.Tensor, target: torch.Tensor) -> MatchResult:
+    def update(self, prob: torch.Tensor, target: torch.Tensor, heat: Optional[torch.Tensor] = None) -> MatchResult:
         if not (isinstance(prob, torch.Tensor) and isinstance(target, torch.Tensor)) or prob.dim() != 3 or tuple(prob.shape) != tuple(target.shape):
             raise ValueError("expected prob and target [B, h, w] of one shape")
+        keypoints = self.refine_kind == "keypoints"
+        if keypoints and heat is None:
+            raise ValueError("refine=dict(kind='keypoints') needs update(prob, target, heat=<the predicted heatmap [B, h, w]>)")
+        if heat is not None and not keypoints:
+            raise ValueError("update(heat=...) needs ObjectMetrics(refine=dict(kind='keypoints', sigma=...))")
+        if keypoints and (not isinstance(heat, torch.Tensor) or tuple(heat.shape) != tuple(prob.shape)):
+            raise ValueError("expected heat [B, h, w] of the shape of prob")
         if not (prob.is_cuda and target.is_cuda):
             raise VkError("object metrics take CUDA tensors (%s / %s): no CPU fallback in this package" % (prob.device, target.device))
         pred = detect(prob, fit=self.fit, fit_outset_px=self.fit_outset_px, max_components=self.max_components, **self.pred_args)
         gt = detect_gt(target, fit=self.fit, fit_outset_px=self.fit_outset_px, max_components=self.max_components)
-        if self.refine is not None:
+        if keypoints:
+            from . import keypoints as KP
+            pred = KP.refine(pred, heat, **self.refine)
+            gt = KP.refine(gt, KP.targets(gt, tuple(prob.shape[1:]), self.kp_sigma), **self.refine)
+        elif self.refine is not None:
             from . import subpix
             pred, gt = subpix.refine(pred, prob, **self.refine), subpix.refine(gt, target.float(), **self.refine)
         res = match(pred, gt, self.thresholds, totals=self._totals)
@@ -223,8 +249,9 @@ class ObjectMetrics:
 
 
 def object_metrics(prob: torch.Tensor, target: torch.Tensor, fit: str = "rect", iou_thresholds=None, max_components: int = 64,
-                   fit_outset_px: int = G.FIT_OUTSET_PX, refine: Optional[dict] = None, **pred_args) -> Dict[str, np.ndarray]:
+                   fit_outset_px: int = G.FIT_OUTSET_PX, refine: Optional[dict] = None, heat: Optional[torch.Tensor] = None,
+                   **pred_args) -> Dict[str, np.ndarray]:
     """Everything in one call: detect both, count, match, summarise.  One read-back at the end."""
     om = ObjectMetrics(fit, iou_thresholds, max_components, fit_outset_px, refine=refine, **pred_args)
-    om.update(prob, target)
+    om.update(prob, target, heat=heat)
     return om.compute()

@@ -11,6 +11,13 @@ the network predicts them directly::
     fine = vk.keypoints.refine(dets, probs2[:, 1])                         # RefinedDetections: to match, render and zoom.merge as it is
     vk.keypoints.peaks(probs2[:, 1]).records()                             # or every local maximum, without a mask
 
+The loss such a model is trained with (csrc/kp_loss.hip behind ``vk_kp_loss``): per-plane terms that join a
+``vk.seglosses`` sum of mode binary or multilabel, in the module form and in the fused step (``vk_unet_loss_kp``)::
+
+    L = vk.seglosses
+    loss = (vk.keypoints.PlaneBCE([0]) + L.DiceLoss("multilabel", classes=[0])
+            + w * vk.keypoints.HeatmapFocalLoss([1], pos_threshold=vk.keypoints.positive_threshold(sigma)))
+
 Coordinates are those of the geometry records: pixel (x, y) lies at the point (x, y).  ``vk.micrographs.truth()`` uses the same
 convention (its vertices are the renderer's 1/16-pixel fixed point divided by 16), so its vertices go to ``targets`` unconverted.
 CUDA tensors only: there is no CPU fallback."""
@@ -22,15 +29,17 @@ from typing import Dict, Iterable, List, Optional, Tuple
 
 import numpy as np
 import torch
+import torch.nn as nn
 
 from . import _lib as L
+from . import _lossfn, lovasz, seglosses
 from . import geometry as G
 from . import instances as I
 from . import subpix as SP
 from ._lib import VkError
 
-__all__ = ["FLAGS", "PEAK_DTYPE", "Peaks", "gaussian_table", "make_targets", "params", "peaks", "postprocess", "refine", "table_radius16",
-           "targets", "vertex_metrics", "with_targets"]
+__all__ = ["FLAGS", "PEAK_DTYPE", "HeatmapFocalLoss", "LossSum", "Peaks", "PlaneBCE", "gaussian_table", "make_targets", "params", "peaks",
+           "positive_threshold", "postprocess", "refine", "table_radius16", "targets", "vertex_metrics", "with_targets"]
 
 FLAGS = dict(L.KP_FLAGS)                       # beside vk.subpix.FLAGS, in the same per-vertex field
 PEAK_DTYPE = np.dtype(L.vk_kp_peak)
@@ -278,3 +287,247 @@ def vertex_metrics(peaks, gt, tol_px: float = 2.0) -> Dict[str, float]:
     fp, fn = len(pk) - tp, len(g) - tp
     return dict(tp=tp, fp=fp, fn=fn, precision=tp / (tp + fp) if tp + fp else 1.0, recall=tp / (tp + fn) if tp + fn else 1.0,
                 mean_dist=float(np.mean(dist)) if dist else 0.0)
+
+
+# ------------------------------------------------------------------------------------------------ losses (csrc/kp_loss.hip)
+MAX_ENTRIES = 2 ** 31 - 1
+_sizeof = C.sizeof
+
+
+def positive_threshold(sigma: float, cutoff: float = 3.0) -> float:
+    """The ``pos_threshold`` that fits targets built from sub-pixel vertices: ``gaussian_table(sigma, cutoff)[128]``.  ``vk_kp_targets``
+    rounds a vertex to 1/16 pixel, so the nearest pixel centre is at most 8 sixteenths away per axis and its squared distance D is at
+    most 128: with this threshold every vertex has between one and four positive pixels wherever it lies inside its pixel.  Needs
+    16 * cutoff * sigma >= 12, so that D = 128 lies inside the disc."""
+    if not 16.0 * float(cutoff) * float(sigma) >= 12.0:
+        raise ValueError("positive_threshold: 16 * cutoff * sigma = %g is below 12: the pixel nearest to a vertex can lie outside the disc"
+                         % (16.0 * float(cutoff) * float(sigma)))
+    return float(gaussian_table(sigma, cutoff)[128])
+
+
+def _planes(planes, who):
+    if isinstance(planes, (int, np.integer)) and not isinstance(planes, bool):
+        planes = (int(planes),)
+    try:
+        out = [int(p) for p in planes]
+        ok = bool(out) and all(float(p) == int(p) and not isinstance(p, bool) for p in planes)
+    except (TypeError, ValueError):
+        out, ok = [], False
+    if not ok or min(out) < 0 or max(out) >= _lossfn.MAX_CLASSES or len(set(out)) != len(out):
+        raise ValueError("%s: planes must name distinct planes in [0, %d), got %r" % (who, _lossfn.MAX_CLASSES, planes))
+    return tuple(sorted(out))
+
+
+def _mask(planes) -> int:
+    return sum(1 << p for p in planes)
+
+
+class _KpAlgebra:
+    """``w * term``, ``term + term`` and ``seg + term`` build a ``vk.keypoints.LossSum``."""
+
+    def _as_kp_sum(self) -> "LossSum":
+        raise NotImplementedError
+
+    def __add__(self, other):
+        if isinstance(other, (int, float)) and not isinstance(other, bool) and other == 0:
+            return self._as_kp_sum()                    # sum([...]) starts from 0
+        me = self._as_kp_sum()
+        if isinstance(other, lovasz._LovaszAlgebra):
+            raise ValueError("a Lovasz term cannot join a vk.keypoints sum: the fused step runs one second part beside vk_seg_loss")
+        if isinstance(other, _KpAlgebra):
+            o = other._as_kp_sum()
+            if me.heat is not None and o.heat is not None:
+                raise ValueError("two heat terms in one sum: a sum holds at most one HeatmapFocalLoss")
+            if me.bce is not None and o.bce is not None:
+                raise ValueError("two plane BCE terms in one sum: a sum holds at most one PlaneBCE")
+            seg = me.seg if o.seg is None else o.seg if me.seg is None else me.seg + o.seg
+            return LossSum(seg, me.heat or o.heat, me.bce or o.bce)
+        if not isinstance(other, seglosses._Algebra):
+            return NotImplemented
+        return LossSum(other._as_sum() if me.seg is None else me.seg + other, me.heat, me.bce)
+
+    __radd__ = __add__
+
+    def __mul__(self, w):
+        w = seglosses._weight(w)
+        if w is None:
+            return NotImplemented
+        me = self._as_kp_sum()
+        return LossSum(None if me.seg is None else w * me.seg, None if me.heat is None else (w * me.heat[0], me.heat[1]),
+                       None if me.bce is None else (w * me.bce[0], me.bce[1]))
+
+    __rmul__ = __mul__
+
+
+class _KpTerm(_KpAlgebra, nn.Module):
+    def __init__(self):
+        super().__init__()
+        self._sum = None
+
+    def forward(self, y_pred, y_true):
+        if self._sum is None:
+            object.__setattr__(self, "_sum", self._as_kp_sum())         # keeps the workspace cache; not a submodule (no cycle)
+        return self._sum(y_pred, y_true)
+
+    def cfg(self, C: int):
+        return self._as_kp_sum().kp_cfg(C)
+
+
+class HeatmapFocalLoss(_KpTerm):
+    """CornerNet's penalty-reduced focal loss on the planes ``planes`` of logits [N, C, H, W] against a heatmap target in [0, 1]: an
+    entry is positive iff y >= ``pos_threshold``; positive -(1 - p)^alpha log p, negative -(1 - y)^beta p^alpha log(1 - p); per plane
+    the sum over (N, H, W) divided by max(number of positives, 1); the mean over the planes.  ``alpha``, ``beta``: integers in 0..8.
+    The default ``pos_threshold`` 1.0 fits integer vertices only (a vertex off the pixel grid has no entry equal to 1): use
+    ``positive_threshold(sigma)`` for the targets of ``make_targets``."""
+
+    def __init__(self, planes=(1,), alpha: int = 2, beta: int = 4, pos_threshold: float = 1.0):
+        super().__init__()
+        self.planes = _planes(planes, "HeatmapFocalLoss")
+        for name, v in (("alpha", alpha), ("beta", beta)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= L.VK_KP_LOSS_MAX_EXP:
+                raise ValueError("HeatmapFocalLoss: %s must be an integer in 0..%d, got %r" % (name, L.VK_KP_LOSS_MAX_EXP, v))
+        if isinstance(pos_threshold, bool) or not isinstance(pos_threshold, (int, float)) or not 0.0 < float(pos_threshold) <= 1.0:
+            raise ValueError("HeatmapFocalLoss: pos_threshold must lie in (0, 1], got %r" % (pos_threshold,))
+        self.alpha, self.beta, self.pos_threshold = int(alpha), int(beta), float(pos_threshold)
+
+    def _as_kp_sum(self):
+        return LossSum(None, (1.0, self), None)
+
+    def extra_repr(self):
+        return "planes=%r, alpha=%d, beta=%d, pos_threshold=%r" % (self.planes, self.alpha, self.beta, self.pos_threshold)
+
+
+class PlaneBCE(_KpTerm):
+    """``torch.nn.BCEWithLogitsLoss(pos_weight)`` on the planes ``planes`` only: the mean over their N H W len(planes) entries.
+    ``pos_weight``: None, one positive number for every plane, or one per plane in the order of ``planes`` as given."""
+
+    def __init__(self, planes=(0,), pos_weight=None):
+        super().__init__()
+        self.planes = _planes(planes, "PlaneBCE")
+        given = [int(planes)] if isinstance(planes, (int, np.integer)) else [int(p) for p in planes]
+        pw = seglosses._pos_weight_list(pos_weight, "PlaneBCE")
+        if pw is not None:
+            if len(pw) not in (1, len(given)):
+                raise ValueError("PlaneBCE: pos_weight holds %d values for %d planes" % (len(pw), len(given)))
+            if not all(v > 0.0 for v in pw):
+                raise ValueError("PlaneBCE: pos_weight must be positive, got %r" % (pw,))
+            pw = dict(zip(given, pw * (len(given) if len(pw) == 1 else 1)))
+        self.pos_weight = pw
+
+    def _as_kp_sum(self):
+        return LossSum(None, None, (1.0, self))
+
+    def extra_repr(self):
+        return "planes=%r, pos_weight=%r" % (self.planes, self.pos_weight)
+
+
+class LossSum(seglosses._Front, _KpAlgebra, nn.Module):
+    """``seg`` (a ``vk.seglosses`` term or sum of mode binary or multilabel, or None) + ``w_heat`` * a ``HeatmapFocalLoss`` +
+    ``w_bce`` * a ``PlaneBCE``: at most one of each, at least one of the two, on planes that do not overlap.  The module form runs
+    ``vk_seg_loss`` and ``vk_kp_loss`` through one autograd function; ``Unet.loss_and_backward(loss=...)`` runs ``vk_unet_loss_kp``.
+    ``last_components``: device tensor [total, pix, focal, dice, jaccard, tversky, mcc, heat, plane_bce] of the last call (unweighted
+    term values; no host sync).  An ``ignore_index`` of the ``vk.seglosses`` part applies to that part alone."""
+
+    def __init__(self, seg, heat, bce):
+        super().__init__()
+        for name, part, cls in (("heat", heat, HeatmapFocalLoss), ("bce", bce, PlaneBCE)):
+            if part is None:
+                continue
+            if not (isinstance(part, tuple) and len(part) == 2 and isinstance(part[1], cls)):
+                raise TypeError("vk.keypoints.LossSum: %s must be None or (weight, %s)" % (name, cls.__name__))
+            if seglosses._weight(part[0]) is None:
+                raise TypeError("vk.keypoints.LossSum: the weight must be a number")
+        if heat is None and bce is None:
+            raise ValueError("vk.keypoints.LossSum: neither a HeatmapFocalLoss nor a PlaneBCE")
+        if heat is not None and bce is not None and set(heat[1].planes) & set(bce[1].planes):
+            raise ValueError("LossSum: HeatmapFocalLoss and PlaneBCE overlap on plane(s) %r"
+                             % (sorted(set(heat[1].planes) & set(bce[1].planes)),))
+        if seg is not None:
+            if isinstance(seg, lovasz._LovaszAlgebra):
+                raise ValueError("a sum with a Lovasz term cannot join a vk.keypoints sum: the fused step runs one second part beside "
+                                 "vk_seg_loss")
+            if not isinstance(seg, seglosses._Algebra):
+                raise TypeError("vk.keypoints.LossSum: seg must be a vk.seglosses term or sum, got %s" % type(seg).__name__)
+            seg = seglosses.LossSum(seg._as_sum().terms)                 # a copy
+            if seg.mode == "multiclass":
+                raise ValueError("LossSum: the vk.seglosses part is of mode 'multiclass'; the keypoint terms are per-plane sigmoid losses "
+                                 "and join a binary or multilabel sum only")
+        self.seg = seg
+        self.heat = None if heat is None else (float(heat[0]), heat[1])
+        self.bce = None if bce is None else (float(bce[0]), bce[1])
+        self._mods = nn.ModuleList([p[1] for p in (self.heat, self.bce) if p is not None])
+        self.mode = None if seg is None else seg.mode
+        self.ignore_index = None if seg is None else seg.ignore_index
+        self.last_components: Optional[torch.Tensor] = None
+        self._ws = {}
+
+    def _as_kp_sum(self):
+        return self
+
+    def resolved_mode(self, C: int) -> str:
+        if self.seg is not None:
+            return self.seg.resolved_mode(C)
+        return _lossfn.check_classes("binary" if C == 1 else "multilabel", C)
+
+    def check_shapes(self, logits: torch.Tensor, target: torch.Tensor) -> str:
+        mode = super().check_shapes(logits, target)
+        self.kp_cfg(int(logits.shape[1]))                    # the planes against C, before anything is asked of the device
+        return mode
+
+    def kp_cfg(self, C: int) -> "L.vk_kp_loss_cfg":
+        """The ``vk_kp_loss_cfg`` of this sum for logits with C planes."""
+        self.resolved_mode(C)
+        c = L.vk_kp_loss_cfg()
+        c.struct_size = _sizeof(L.vk_kp_loss_cfg)
+        c.alpha, c.beta, c.pos_threshold = 2, 4, 1.0
+        for name, part in (("HeatmapFocalLoss", self.heat), ("PlaneBCE", self.bce)):
+            if part is not None and max(part[1].planes) >= C:
+                raise ValueError("%s(planes=%r) names a plane >= C = %d" % (name, part[1].planes, C))
+        if self.heat is not None:
+            w, t = self.heat
+            c.heat_planes, c.w_heat, c.alpha, c.beta, c.pos_threshold = _mask(t.planes), w, t.alpha, t.beta, t.pos_threshold
+        if self.bce is not None:
+            w, t = self.bce
+            c.bce_planes, c.w_bce = _mask(t.planes), w
+            if t.pos_weight is not None:
+                c.has_pos_weight = 1
+                for i in range(16):
+                    c.pos_weight[i] = t.pos_weight.get(i, 1.0)
+        return c
+
+    def seg_cfg(self, C: int):
+        return None if self.seg is None else self.seg.cfg(C)
+
+    def workspace(self, N: int, C: int, HW: int, device) -> torch.Tensor:
+        """the device scratch of vk_kp_loss for this shape (cached per shape)"""
+        if N * C * HW > MAX_ENTRIES:
+            raise VkError("vk.keypoints.LossSum: %d logits in one call, at most 2^31 - 1" % (N * C * HW))
+        key = (N, C, HW, str(device))
+        ws = self._ws.get(key)
+        if ws is None:
+            nbytes = L.lib().vk_kp_loss_workspace_bytes(N, C, HW)
+            if nbytes == 0:
+                raise VkError("vk_kp_loss_workspace_bytes refuses N=%d C=%d HW=%d" % (N, C, HW))
+            ws = self._ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        return ws
+
+    def _run(self, x, y, dl):
+        N, Cc, H, W = x.shape
+        HW = H * W
+        kcfg = self.kp_cfg(Cc)
+        lib = L.lib()
+        st = L.current_stream()
+        out = torch.zeros(16, dtype=torch.float32, device=x.device)
+        if self.seg is not None:
+            sws = torch.empty(lib.vk_seg_loss_workspace_bytes(N, Cc, HW), dtype=torch.uint8, device=x.device)
+            L.check(lib.vk_seg_loss(self.seg.cfg(Cc), N, Cc, HW, x.data_ptr(), y.data_ptr(), sws.data_ptr(), sws.numel(), out.data_ptr(),
+                                    L.ptr(dl), 1.0, st), "vk_seg_loss")
+        ws = self.workspace(N, Cc, HW, x.device)
+        L.check(lib.vk_kp_loss(kcfg, N, Cc, HW, x.data_ptr(), y.data_ptr(), ws.data_ptr(), ws.numel(), out[8:].data_ptr(), None, L.ptr(dl),
+                               1.0, 1 if self.seg is not None else 0, st), "vk_kp_loss")
+        total = out[0] + out[8]
+        self.last_components = torch.cat([total.reshape(1), out[1:6], out[7:8], out[9:11]])
+        return total, None
+
+    def extra_repr(self):
+        return "w_heat=%r, w_bce=%r" % (None if self.heat is None else self.heat[0], None if self.bce is None else self.bce[0])

@@ -161,7 +161,9 @@ class Segmenter:
         refinement with the letterbox's affine row, then (``zoom=True``) the second pass of ``vk.zoom``: one window per detection cut
         from the image at the finest scale that shows it whole, segmented, fitted and refined there.  Returns the detection list of
         ``vk.subpix.postprocess`` (sorted by area; ``d1``, ``d2``, ``d_mean``, ``box_subpix`` in source pixels), with ``zoom_status``
-        and ``zoom_scale`` per row after the zoom pass.  ``kw``: ``method`` and the arguments of ``vk.zoom.refine_detections``."""
+        and ``zoom_scale`` per row after the zoom pass.  ``kw``: ``method`` and the arguments of ``vk.zoom.refine_detections``.
+        ``method="heatmap"`` (with ``zoom=False``; a model with a mask plane and a vertex heatmap plane): the vertices come from
+        ``vk.keypoints.refine`` on the sigmoid of plane 1 (``refine_args`` go to it) in place of ``vk.subpix.refine``."""
         from .zoom import measure
         return measure(self, img_bgr, fit=fit, zoom=zoom, **kw)
 

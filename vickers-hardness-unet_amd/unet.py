@@ -50,7 +50,7 @@ class _Plan:
         dev = model._flat["params"].device
         self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
         self.loss_out = torch.zeros(4, dtype=torch.float32, device=dev)
-        self._seg_out = self._lovasz_out = None       # the result buffers of the loss= routes: made at a route's first step on this plan
+        self._seg_out = self._lovasz_out = self._kp_out = None       # the result buffers of the loss= routes: made at a route's first step on this plan
         self.weights_version = None
         self.mask = None                    # trainable flags the engine holds (vk_unet_set_trainable); None: not pushed yet
         self.bn_frozen = None               # BatchNorm modes the engine holds (vk_unet_set_bn_frozen); None: not pushed (all train)
@@ -116,6 +116,15 @@ class _Plan:
                                 torch.tensor([0, 1, 2, 3, 4, 5, 7, 8], dtype=torch.int64, device=dev),
                                 torch.empty(8, dtype=torch.float32, device=dev))
         return self._lovasz_out
+
+    def kp_out(self):
+        """(the 16 floats vk_unet_loss_kp writes, the indices of the 9 that are reported, the 9 floats they are gathered into)."""
+        if self._kp_out is None:
+            dev = self.ws.device
+            self._kp_out = (torch.zeros(16, dtype=torch.float32, device=dev),
+                            torch.tensor([0, 1, 2, 3, 4, 5, 7, 8, 9], dtype=torch.int64, device=dev),
+                            torch.empty(9, dtype=torch.float32, device=dev))
+        return self._kp_out
 
     def debug_tensor(self, name: str) -> torch.Tensor:
         """Copy of a named intermediate (NHWC) — parity/debug only."""
@@ -562,11 +571,26 @@ class Unet(nn.Module):
         ``loss``: a ``vk.seglosses`` term or sum instead of ``mode`` (the two exclude each other): the same step with that loss
         (vk_unet_loss_cfg); returns a device tensor [total, pix, focal, dice, jaccard, tversky] of a buffer of its own.  A
         ``vk.lovasz.LovaszLoss`` or ``vk.lovasz.LossSum`` runs vk_unet_loss_lovasz instead and returns
-        [total, pix, focal, dice, jaccard, tversky, mcc, lovasz]."""
+        [total, pix, focal, dice, jaccard, tversky, mcc, lovasz].  A ``vk.keypoints`` term or ``vk.keypoints.LossSum`` runs
+        vk_unet_loss_kp and returns [total, pix, focal, dice, jaccard, tversky, mcc, heat, plane_bce]."""
         if loss is not None:
             if mode is not None:
                 raise ValueError("loss_and_backward: give mode= or loss=, not both")
             from . import lovasz, seglosses
+            from . import keypoints
+            if isinstance(loss, keypoints._KpAlgebra):
+                S = loss._as_kp_sum()
+                kcfg, scfg = S.kp_cfg(self.classes), S.seg_cfg(self.classes)
+
+                def launch(plan, logits, y, st):
+                    ws = S.workspace(plan.N, self.classes, plan.H * plan.W, logits.device)
+                    check(lib().vk_unet_loss_kp(plan.h, scfg, kcfg, logits.data_ptr(), y.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                plan.kp_out()[0].data_ptr(), float(grad_scale), st), "vk_unet_loss_kp")
+
+                plan = self._fused_step(x, y, dtype, False, "loss=<multiclass>", True, launch)
+                out, pick, picked = plan.kp_out()
+                S.last_components = torch.index_select(out, 0, pick, out=picked)
+                return picked
             if isinstance(loss, lovasz._LovaszAlgebra):
                 S = loss._as_lovasz_sum()
                 lcfg, scfg = S.lovasz_cfg(self.classes), S.seg_cfg(self.classes)

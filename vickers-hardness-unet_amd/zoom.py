@@ -227,16 +227,30 @@ def _measure(seg, img_bgr, fit: str, zoom: bool, method: str, **kw):
     """The steps of ``measure`` -> (the image on the device, the letterbox metadata, the logits [S, S], the first pass's detections, the
     refined ones)."""
     from . import prepost as PP
+    heatmap = method == "heatmap"         # vk.keypoints: the vertices from plane 1 of a two-plane model, in place of vk.subpix
+    if heatmap:
+        if zoom:
+            raise ValueError("method='heatmap' needs zoom=False: the zoom pass with a heatmap read-out is not implemented")
+        classes = getattr(seg.model, "classes", None)
+        if isinstance(classes, int) and classes < 2:
+            raise ValueError("method='heatmap' needs a model with a mask plane and a heatmap plane, this one has %d plane(s)" % classes)
     src = PP._as_device_u8(img_bgr, seg.device)
     h, w = int(src.shape[0]), int(src.shape[1])
     size = int(seg.img_size)
     with torch.no_grad():
         x, meta = PP.preprocess(src, size, "centered", seg.device)
-        logits = seg.model(x)[:, 0].float()
+        planes = seg.model(x)
+        if heatmap and planes.shape[1] < 2:
+            raise ValueError("method='heatmap' needs a model with a mask plane and a heatmap plane, this one has %d plane(s)"
+                             % planes.shape[1])
+        logits = planes[:, 0].float()
         prob = torch.sigmoid(logits)
     dets = G.detect(prob, fit=fit)
     aff = SP.letterbox_affine(h, w, size, "centered")
-    if zoom:
+    if heatmap:
+        from . import keypoints as KP
+        fine = KP.refine(dets, torch.sigmoid(planes[:, 1].float()), affine=aff, **(kw.get("refine_args") or {}))
+    elif zoom:
         fine = refine_detections(seg.model, [src], dets, prob, affine=aff, S=size, method=method, **kw)
     else:
         fine = SP.refine(dets, prob, method=method, affine=aff, **(kw.get("refine_args") or {}))

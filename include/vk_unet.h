@@ -848,7 +848,8 @@ int vk_head_fwd_multi(vk_dtype dtype, int N, int H, int W, int C, const vk_src* 
 size_t vk_head_multi_workspace_bytes(int C);
 int vk_head_bwd_multi(vk_dtype dtype, int N, int H, int W, int C, const vk_src* src, const float* w, const float* dlogits, void* dy,
                       float* dw, float* dbias, const vk_bnr* bnr, void* workspace, size_t workspace_bytes, void* stream);
-/* Device scratch of the two losses below for logits [N][C][HW] (8-byte aligned). */
+/* Device scratch of the two losses below for logits [N][C][HW] (8-byte aligned).  It need not be cleared or kept between calls: every
+ * row of partials that a call reads it has written first; a workspace of exactly this size is accepted and nothing past it is touched. */
 size_t vk_multi_loss_workspace_bytes(int N, int C, int HW);
 /* loss = w_bce * BCEWithLogitsLoss()(x, y) + w_dice * smp DiceLoss("multilabel")(x, y); x, y fp32 [N][C][HW].
  * Per class c: I = sum sigmoid(x) y, P = sum sigmoid(x), T = sum y over (N, HW) in fp64 (per-workgroup partials added in a fixed
@@ -906,7 +907,8 @@ typedef struct vk_seg_loss_cfg {
   float w_mcc, mcc_eps;    /* appended: no earlier field moved */
 } vk_seg_loss_cfg;
 size_t vk_seg_loss_cfg_size(void);
-/* Device scratch for logits [N][C][HW] in any mode (8-byte aligned). */
+/* Device scratch for logits [N][C][HW] in any mode (8-byte aligned).  It need not be cleared or kept between calls; a workspace of
+ * exactly this size is accepted and nothing past it is touched. */
 size_t vk_seg_loss_workspace_bytes(int N, int C, int HW);
 /* loss_out float[8] = {total, pix, focal, dice, jaccard, tversky, bad labels, mcc} (absent terms 0); dlogits (optional) = grad_scale *
  * d total / dx, exactly 0 at ignored entries.  A multiclass label that is neither in [0, C) nor ignore_index is an argument error
@@ -1259,7 +1261,8 @@ typedef struct vk_kp_loss_cfg {
 } vk_kp_loss_cfg;
 size_t vk_kp_loss_cfg_size(void);
 /* Device scratch (8-byte aligned; the caller owns it); 0 for arguments out of range: N, HW >= 1, HW <= 2^28, N C <= 65535,
- * N C HW <= 2^31 - 1. */
+ * N C HW <= 2^31 - 1.  It need not be cleared or kept between calls; a workspace of exactly this size is accepted and nothing past it
+ * is touched. */
 size_t vk_kp_loss_workspace_bytes(int N, int C, int HW);
 /* loss_out float[8] = {total, heat, bce, 0, ...}; positives (optional) int64[16]: P_c of the heat planes, 0 elsewhere; dlogits
  * (optional) = grad_scale * d total / dx: accumulate = 0 writes every entry (planes with neither rule get 0), accumulate = 1 adds

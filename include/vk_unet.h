@@ -291,9 +291,16 @@ typedef struct {
 
 /* uint8 BGR [h][w][3] (device) -> float32 [3][S][S] RGB planes, ((v/255) - mean) / std with the ImageNet constants */
 int vk_letterbox_preprocess(const vk_letterbox_desc* d, const uint8_t* bgr, float* x_nchw, void* stream);
-/* logits [S][S] -> uint8 [h][w] in {0,255}: (sigmoid >= thresh), crop, INTER_NEAREST back to the original size */
+/* logits [S][S] -> uint8 [h][w] in {0,255}: (sigmoid >= thresh), crop, INTER_NEAREST back to the original size.
+ * The comparison is >=: a sigmoid exactly on the threshold is foreground (a zero logit at 0.5; every logit from 17 up at 1.0, where
+ * the float32 sigmoid is exactly 1; every logit at 0.0).  vk_seg_metrics below uses the strict >, as the reference's metrics do.
+ * A NaN logit is background at every threshold (NaN >= t is false); +-inf give sigmoid 1 / 0.
+ * mask_hw needs no alignment: rows are stored as 32-bit words only when w % 4 == 0 and mask_hw is 16-byte aligned, bytes otherwise. */
 int vk_letterbox_postprocess_mask(const vk_letterbox_desc* d, const float* logits, float thresh, uint8_t* mask_hw, void* stream);
-/* logits [S][S] -> float32 [h][w] in [0,1]: sigmoid, crop, INTER_LINEAR back to the original size (copy when equal), clip */
+/* logits [S][S] -> float32 [h][w] in [0,1]: sigmoid, crop, INTER_LINEAR back to the original size (copy when equal), clip.
+ * A NaN logit gives NaN in every output pixel one of whose four taps reads it, also where that tap's weight is 0 (NaN * 0), as
+ * numpy's arithmetic and np.clip give: the clip keeps a NaN, it does not turn it into 0.  Small and large outputs take two kernels
+ * that evaluate the same expression: the same bits.  prob_hw needs 4-byte alignment only (16-byte stores when it has it and w % 4 == 0). */
 int vk_letterbox_postprocess_prob(const vk_letterbox_desc* d, const float* logits, float* prob_hw, void* stream);
 /* The same for a C-class logit map [C][S][S] (fp32 class planes, 1 <= C <= 16), same descriptor and arithmetic; with C == 1 the mask
  * and multi-label probability calls give the bits of the two calls above.
@@ -473,12 +480,20 @@ size_t vk_augment_workspace_bytes(int n, int size);
 
 /* uint8 BGR [h][w][3] -> uint8 RGB [S][S][3]: cv2.resize(INTER_LINEAR) to nh x nw at (top, left), constant border */
 int vk_letterbox_u8(const vk_letterbox_desc* d, const uint8_t* bgr, uint8_t* rgb_sq, void* stream);
-/* uint8 mask [h][w] (row stride d->src_stride bytes) -> {0,1} [S][S]: (m > 0), cv2.resize(INTER_NEAREST), border 0 */
+/* uint8 mask [h][w] (row stride d->src_stride bytes) -> {0,1} [S][S]: (m > 0), cv2.resize(INTER_NEAREST), border 0 (pad_value is not
+ * used).  Both calls read w (3 * w) bytes of a row and never its padding up to src_stride; a descriptor with nh or nw below 1 (a 1 x 50
+ * image at size 8 under the train convention) is VK_ERR_ARG before any launch. */
 int vk_letterbox_mask_u8(const vk_letterbox_desc* d, const uint8_t* mask_hw, uint8_t* mask_sq, void* stream);
 /* images_rgb uint8 [n_items][S][S][3], masks uint8 [n_items][S][S] in {0,1} (device); index_dev int32 [n] (device): the dataset
  * item of every sample; params_host [n]: validated on the host, then copied to params_dev (device scratch, n * sizeof).
  * color_tables (device, int32 [VK_AUG_TABLE_INTS]) and workspace (device, vk_augment_workspace_bytes(n, size)) are needed only
- * when a sample has photo == 2 and may be null otherwise; CLAHE needs size % 8 == 0 (8 x 8 tiles without padding). */
+ * when a sample has photo == 2 and may be null otherwise; CLAHE needs size % 8 == 0 (8 x 8 tiles without padding).
+ * index_dev[i] is clamped to 0 .. n_items - 1 on the device: an index below 0 gives item 0, one above the store its last item, the
+ * same bits as that item asked for by its own index; nothing outside the store is read.
+ * workspace: written only when a sample has photo == 2, and then only inside sample i's own slot of
+ * vk_augment_workspace_bytes(1, size) bytes at i times that size, for the samples that drew CLAHE; every byte read is written first by
+ * the same call, so its previous contents never reach the result and it need not be cleared.  x and y are written in full
+ * (n * 3 * size * size and n * size * size floats), nothing either side of them. */
 int vk_augment_batch(int n, int size, int n_items, const uint8_t* images_rgb, const uint8_t* masks, const int* index_dev,
                      const vk_aug_params* params_host, void* params_dev, const int* color_tables, void* workspace,
                      size_t workspace_bytes, float* x, float* y, void* stream);
@@ -952,6 +967,8 @@ int vk_lovasz_flat(const float* errors, const uint8_t* flag, int S, int64_t L, v
  * per image i of `per_image` elements, pred = (p > threshold) as 0/1, I = sum pred*t, P = sum pred, T = sum t;
  * dice_i = (2 I + eps) / (P + T + eps), iou_i = (I + eps) / (P + T - I + eps) in fp32.
  * pred: probabilities, or logits when from_logits != 0 (then p = 1 / (1 + expf(-x)) first).
+ * The comparison is the strict >: a probability exactly on the threshold, and a zero logit at 0.5, is a miss (post-processing above
+ * uses >=).  pred and target need 4-byte alignment only: 16-byte loads are used when both have it and per_image % 4 == 0.
  * out (device, 2 + 2 n_images floats): [0] mean dice, [1] mean iou, [2 + 2i], [3 + 2i] = image i.
  * workspace: vk_seg_metrics_workspace_bytes(n_images) of 8-byte aligned device scratch; afterwards it holds the
  * fp64 sums {I, P, T} per image.  One pass over both tensors + one single-workgroup launch; bit-reproducible for 0/1 targets. */

@@ -139,5 +139,6 @@ def test_argument_errors(dataset):
         ds.batch([0], draws=[dict(vk.augment.IDENTITY, photo=3, blur_ksize=4)])
     with pytest.raises(vk.VkError):
         vk.DeviceDataset([np.zeros((4, 4, 3), np.uint8)], [np.zeros((4, 4), np.uint8)], device="cpu")
-    x, _, _ = ds.batch([99])                                     # out-of-range item index is clamped on the device, never read out of bounds
-    assert torch.isfinite(x).all()
+    x, y, _ = ds.batch([99, -5])                                 # out-of-range item index is clamped on the device, never read out of bounds:
+    xc, yc, _ = ds.batch([3, 0])                                 # the last and the first item, bit for bit
+    assert torch.isfinite(x).all() and torch.equal(x, xc) and torch.equal(y, yc)

@@ -25,6 +25,9 @@ namespace vk {
 
 __device__ __forceinline__ int fix11(float w) { return __float2int_rn(w * 2048.f); }   // saturate_cast<short>(w * INTER_RESIZE_COEF_SCALE)
 
+// np.clip(v, 0, 1): a NaN stays a NaN (fminf / fmaxf would return the other operand and hide it as 0)
+__device__ __forceinline__ float clip01(float v) { return v < 0.f ? 0.f : (v > 1.f ? 1.f : v); }
+
 __global__ __launch_bounds__(256) void k_letterbox_pre(const LbParams p, const uint8_t* __restrict__ src, float* __restrict__ out) {
 #pragma clang fp contract(off)
   const int x = blockIdx.x * 64 + (threadIdx.x & 63);
@@ -103,7 +106,7 @@ __global__ __launch_bounds__(256) void k_letterbox_prob(const LbParams p, const 
     const float h1 = p10 * a0 + p11 * a1;
     o = h0 * b0 + h1 * b1;
   }
-  prob[(size_t)y * p.w + x] = fminf(fmaxf(o, 0.f), 1.f);
+  prob[(size_t)y * p.w + x] = clip01(o);
 }
 
 // Post-processing of large outputs, both flavours: a workgroup owns a 256 x 16 block of the ORIGINAL-size output (thread = 4 consecutive
@@ -177,6 +180,7 @@ __global__ __launch_bounds__(256) void k_letterbox_post(const LbParams p, const 
       sx1[j] = min(sx[j] + 1, p.nw - 1);
     }
   }
+  const bool same = p.nh == p.h && p.nw == p.w;
   const bool vec = (p.w & 3) == 0 && (reinterpret_cast<uintptr_t>(outv) & 15) == 0;      // x0 + 3 < w, aligned vector stores
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -205,10 +209,14 @@ __global__ __launch_bounds__(256) void k_letterbox_post(const LbParams p, const 
       float o[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
+        if (same) {      // the crop has the original size: a copy, as in k_letterbox_prob (no neighbour is read, so a NaN stays in its pixel)
+          o[j] = clip01(tap(sy, sx[j]));
+          continue;
+        }
         const float a0 = 1.f - fx[j], a1 = fx[j];
         const float h0 = tap(sy, sx[j]) * a0 + tap(sy, sx1[j]) * a1;
         const float h1 = tap(sy1, sx[j]) * a0 + tap(sy1, sx1[j]) * a1;
-        o[j] = fminf(fmaxf(h0 * b0 + h1 * b1, 0.f), 1.f);
+        o[j] = clip01(h0 * b0 + h1 * b1);
       }
       if (vec) {
         *reinterpret_cast<f32x4_t*>(out) = f32x4_t{o[0], o[1], o[2], o[3]};
